@@ -1,6 +1,11 @@
 """policy-steps/sec of the VLN-CE policy hot path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the one JSON line (`metric`, `value`,
+`ms_per_step`, ...).  `--full` adds everything else the line can carry: the encode_ahead figure,
+`roofline`, the act() latencies, the fp32-MFMA-only child run and `cpu_baseline`.
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy.
 
 N > 1: one rank per GPU.  Under a launcher (torch.distributed.run sets RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_*) the process is one of the N ranks; started plainly, `python bench.py
@@ -245,7 +250,7 @@ def f32_mfma_compare(args):
     bf16-plane kernel.  Reported beside `value`, never as `value`."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup",
-           str(args.warmup), "--num-envs", str(args.num_envs), "--no-cpu-baseline",
+           str(args.warmup), "--num-envs", str(args.num_envs), "--full", "--no-cpu-baseline",
            "--no-f32-compare"]
     try:
         out = subprocess.run(cmd, env=dict(os.environ, VLNCE_CONV_MATH="f32"), capture_output=True,
@@ -451,6 +456,137 @@ def act_latency(policy, batch, dev, sizes=(1, 4, 8), iters=20):
     return out
 
 
+def cma_roofline(conv, num_envs):
+    """`roofline` of the headline line (--full): the forward convolution launches of the two
+    trunks, timed by conv_kernel_time, against their per-launch floor."""
+    # the attributed launches are the forward convolutions of the two trunks (in the
+    # trainable-encoder variant the data-gradient launches are the same kernel again)
+    conv_flop = CONV_GFLOP_PER_ENV * 1e9 * num_envs
+    conv_ms, n_conv = conv["conv_ms"], conv["n"]
+    ok = conv["reason"] is None
+    achieved = conv_flop / (conv_ms * 1e-3) / 1e12 if ok else None
+    floor_rate = conv_flop / (conv["floor_ms"] * 1e-3) / 1e12 if ok else None
+    # per kernel family, from the library's own dispatch record (vlnce_conv2d_last_path)
+    fam = {0: "fp32_mfma", 1: "bf16_planes_x3", 2: "bf16_planes_p3", 3: "bf16_planes_m3"}
+    paths = {fam.get(k, str(k)): v for k, v in conv["by_path"].items()}
+    bf = [v for k, v in paths.items() if k.startswith("bf16")]
+    bf_ms, bf_flop = sum(v["ms"] for v in bf), sum(v["flop"] for v in bf)
+    f32 = paths.get("fp32_mfma", {"ms": 0.0, "flop": 0.0, "launches": 0})
+
+    def tf(v):
+        return round(v["flop"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else None
+
+    return {"schema": 3,
+            "schema_is": "3 (round 6): the plane kernels issue `bf16_pipe."
+                         "hw_flops_per_algorithmic_flop` 16-bit MFMA FLOPs per fp32 FLOP "
+                         "(3 with fp16 planes, 6 with bf16 planes) and the per-launch "
+                         "floor prices that count; 2 (round 5): `frac` / `peak` = the "
+                         "per-launch max(HBM, MFMA) floor, the fp32-MFMA-peak figure "
+                         "under `fp32_mfma_peak`; 1 (rounds 1-4): frac = achieved / fp32 "
+                         "MFMA peak",
+            "bound": "mfma",
+            "kernel": "conv2d fwd of the two visual trunks: conv_p3_kernel (stride-1 "
+                      "KxK: A transformed once per workgroup into an LDS patch, B "
+                      "fragments from L2), conv_u3_kernel (wide 1x1: no producer "
+                      "waves, the matrix waves transform the next K-chunk between "
+                      "their MFMAs), conv_s3_kernel (short-K 1x1 expansions: whole K "
+                      "resident, tile n+1's loads under tile n's stores), "
+                      "conv_x3_kernel (the other 1x1 / strided: im2col K-tiles through "
+                      "LDS, 8 producer + 8 matrix waves), conv_m3_kernel (small "
+                      "launches -- the depth trunk: A fragments straight from global "
+                      "memory, reduction split over a workgroup's waves) and "
+                      "stem7_kernel (the 7x7/s2 RGB stem straight from the frames); "
+                      "all six: fp32 operands "
+                      + ("split into fp16 planes (activations a1 + a2, weights b1 + b2, "
+                         "11 + 11 mantissa bits each), 3 x v_mfma_f32_32x32x16_f16 "
+                         "(a1 b1 + a1 b2 + a2 b1) per 32x32x16 block"
+                         if plane_products() == 3 else
+                         "split exactly into 3 bf16 planes, 6 x "
+                         "v_mfma_f32_32x32x16_bf16 per 32x32x16 block")
+                      + ", fp32 accumulate, "
+                      "train-mode BatchNorm column sums taken in the epilogue; "
+                      "igemm_kernel (v_mfma_f32_32x32x2_f32) for the depth stem and "
+                      "the handful-of-tiles layers",
+            "achieved": round(achieved, 2) if ok else None,
+            "peak": round(floor_rate, 2) if ok else None, "unit": "TFLOP/s",
+            "frac": round(conv["floor_ms"] / conv_ms, 4) if ok else None,
+            "peak_is": "the algorithmic fp32 rate these launches would reach if EACH sat "
+                       "on its own hardware roofline, max(algorithmic bytes / achievable "
+                       "HBM rate, instruction FLOPs / peak of the pipe it runs on) -- "
+                       "`per_launch_floor` below has the terms; frac = achieved / peak = "
+                       "floor_ms / kernel_ms_per_step.  The same `achieved` against the "
+                       "fp32 MFMA peak (the reference arithmetic's roofline, which the "
+                       "bf16-plane kernels can exceed) is `fp32_mfma_peak`; the hardware "
+                       "FLOPs of the bf16-plane launches against their pipe `bf16_pipe`",
+            "fp32_mfma_peak": {"peak": FP32_MFMA_PEAK_TFLOPS,
+                               "frac": (round(achieved / FP32_MFMA_PEAK_TFLOPS, 4)
+                                        if ok else None)},
+            "bf16_pipe": {"instruction": ("v_mfma_f32_32x32x16_f16" if plane_products() == 3
+                                          else "v_mfma_f32_32x32x16_bf16"),
+                          "hw_flops_per_algorithmic_flop": plane_products(),
+                          "peak": BF16_MFMA_PEAK_TFLOPS,
+                          "launches": sum(v["launches"] for v in bf),
+                          "kernel_ms_per_step": round(bf_ms, 3),
+                          "achieved_algorithmic_tflops": (
+                              round(bf_flop / (bf_ms * 1e-3) / 1e12, 2) if bf_ms else None),
+                          "frac": (round(plane_products() * bf_flop / (bf_ms * 1e-3) / 1e12
+                                         / BF16_MFMA_PEAK_TFLOPS, 4) if bf_ms and ok
+                                   else None),
+                          "by_kernel": {k: {"launches": v["launches"],
+                                            "ms": round(v["ms"], 3), "tflops": tf(v)}
+                                        for k, v in paths.items() if k.startswith("bf16")}},
+            "fp32_mfma": {"instruction": "v_mfma_f32_32x32x2_f32",
+                          "peak": FP32_MFMA_PEAK_TFLOPS, "launches": f32["launches"],
+                          "kernel_ms_per_step": round(f32["ms"], 3),
+                          "achieved_tflops": tf(f32),
+                          "frac": (round(tf(f32) / FP32_MFMA_PEAK_TFLOPS, 4)
+                                   if f32["ms"] and ok else None)},
+            "flop_check": {"per_launch_geometry_gflop": round(conv["flop"] / 1e9, 2),
+                           "survey_a3_gflop": round(conv_flop / 1e9, 2)},
+            "arithmetic": (
+                "fp32-class: a = a1 + a2 with a1 = fp16(a), a2 = fp16((a - a1) 2^11) / 2^11 "
+                "(11 + 11 mantissa bits and the sign of a2, residual <= 2^-22 |a|), the "
+                "same for the weights; a1 b1 + a1 b2 + a2 b1 accumulated in fp32 at the "
+                "common scale 2^11 (dropped a2 b2 <= 2^-22); against an fp64 convolution "
+                "as close as the six-product bf16 form (half as many fp32 accumulator "
+                "updates; tests/test_kernels_gpu.py::test_conv_p3_matches_fp64_better_"
+                "than_1e_6 holds both to 1e-6 rms); |x| < 65504, |w| < 32; "
+                "VLNCE_CONV_MATH=bf16 selects three bf16 planes / six products, =f32 the "
+                "fp32-MFMA kernel everywhere" if plane_products() == 3 else
+                "fp32-class: operands are represented exactly by three bf16 "
+                "planes (round-to-nearest split), products are exact, six of "
+                "the nine are kept (dropped <= 2^-26 relative), accumulation "
+                "is fp32; measured relative rms error vs an fp64 convolution "
+                "1.6-2.8x torch's own fp32 convolution on the same operands "
+                "(profiles/archive/r03_e_conv_accuracy_*.txt); VLNCE_CONV_MATH=f32 "
+                "selects the fp32-MFMA kernel everywhere"),
+            "per_launch_floor": {
+                "what": "sum over the conv launches of max(algorithmic bytes / "
+                        "achievable HBM rate, instruction FLOPs / the peak of the pipe "
+                        "the launch runs on): the time the launches would take if "
+                        "each sat on its own roofline; hbm_bound = the launches whose "
+                        "HBM term is the larger one",
+                "hbm_achievable_TBps": HBM_ACHIEVABLE_TBS, "hbm_peak_TBps": HBM_PEAK_TBS,
+                "floor_ms": round(conv["floor_ms"], 3),
+                "frac": round(conv["floor_ms"] / conv_ms, 4) if ok else None,
+                "algorithmic_GB": round(conv["bytes"] / 1e9, 3),
+                "hbm_bound": {"launches": conv["hbm_bound_n"],
+                              "ms": round(conv["hbm_bound_ms"], 3),
+                              "floor_ms": round(conv["hbm_floor_ms"], 3),
+                              "achieved_TBps": (round(
+                                  conv["hbm_floor_ms"] * HBM_ACHIEVABLE_TBS
+                                  / conv["hbm_bound_ms"], 2)
+                                  if conv["hbm_bound_ms"] > 0 else None)}},
+            "launches_per_step": n_conv,
+            "avg_launch_ms": round(conv_ms / max(n_conv, 1), 4),
+            "kernel_ms_per_step": round(conv_ms, 3),
+            "eager_single_stream_trunks_ms": round(conv["eager_trunks_ms"], 3),
+            "timing": "HIP events per launch behind a device-side backlog "
+                      "(GPU-paced), empty-pair cost subtracted, min of 3 passes",
+            "invalid_reason": conv["reason"],
+            "traffic": pmc_traffic(n_conv)}
+
+
 def self_launch(n):
     """`python bench.py --gpus N` with no launcher around it (no WORLD_SIZE in the environment):
     re-run this very command line as N ranks, one per GPU, under torch.distributed.run on this
@@ -487,6 +623,37 @@ def exchange_fields(ex):
             "allreduce": {"buckets": ex["buckets"], "issued_from_backward_hooks": ex["issued_from_hooks"],
                           "exposed_ms": round(ex["exposed_ms"], 3),
                           "what": "rank 0, last timed step; hidden = ran under backward"}}
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, readbacks, policy):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, so that two builds can be
+    compared output for output on the same seeded inputs.  An update returns its host read-backs
+    and leaves the policy's parameters and running statistics changed in place:
+    `step_readbacks.npy` (float64), `trainable_params.npy` and `float_buffers.npy` (float32, each
+    tensor flattened in `named_parameters` / `named_buffers` order).  A group larger than its share
+    of DUMP_BYTES is written as a fixed, seeded sample of its elements (`<name>_index.npy` holds
+    the sampled positions)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "step_readbacks.npy"),
+            np.asarray([float(v) for v in readbacks], dtype=np.float64))
+    # (group, tensors, its share of the budget in bytes)
+    groups = [("trainable_params", [p for _, p in policy.named_parameters() if p.requires_grad],
+               DUMP_BYTES * 7 // 8 - 4096),
+              ("float_buffers", [b for _, b in policy.named_buffers() if b.is_floating_point()],
+               DUMP_BYTES // 8)]
+    for name, ts, share in groups:
+        flat = torch.cat([t.detach().reshape(-1).float() for t in ts]) if ts else torch.zeros(0)
+        if 4 * flat.numel() > share:   # sampled: 4 bytes per value + 8 per float64 index
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))
+            idx = idx[:share // 12].sort().values
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.numpy().astype(np.float64))
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), flat.cpu().numpy().astype(np.float32))
 
 
 def synth_pano_batch(n, hw, tokens, device, seed=1):
@@ -601,8 +768,10 @@ def secondary_policy_bench(args, dev, rank, world, sim, use_dist, dev_sync):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
     log(f"timed region: {args.steps} steps in {elapsed:.3f}s; last step's read-backs {last}")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, policy)
     roof = None
-    if rank == 0 and not sim:
+    if rank == 0 and not sim and args.full:
         if way:   # the 12 panorama frames + the masked history frame, as _encode_frames hands them over
             wobs, wmask = samples[0][0], samples[0][6].reshape(-1)
 
@@ -661,7 +830,7 @@ def secondary_policy_bench(args, dev, rank, world, sim, use_dist, dev_sync):
             **exchange_fields(exchange)}
         if roof:
             line["roofline"] = roof
-        if world == 1 and not sim and not args.no_cpu_baseline:
+        if world == 1 and not sim and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(n, hw, L, timeout_s=240 if way else 150,
                                                 which=args.policy)
         final = json.dumps(line)
@@ -692,9 +861,17 @@ def main():
     ap.add_argument("--tokens", type=int, default=None, help="default 80 (cma, seq2seq) / 200 (waypoint)")
     ap.add_argument("--bn", choices=["train", "eval"], default="train",
                     help="train = as constructed by the reference (batch statistics)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the encode_ahead figure, roofline, act() latencies, "
+                         "the fp32-MFMA-only child run and the CPU baseline (a plain run times the "
+                         "steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (read-backs, parameters and "
+                         "running statistics after it) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-f32-compare", action="store_true",
-                    help="skip the child run with every convolution on the fp32 MFMA instruction")
+                    help="with --full: skip the child run with every convolution on the fp32 MFMA "
+                         "instruction")
     ap.add_argument("--trainable-encoders", action="store_true",
                     help="MODEL.{RGB,DEPTH}_ENCODER.trainable=True: trunks get dgrad/wgrad too")
     ap.add_argument("--pmc-step", action="store_true",
@@ -703,8 +880,8 @@ def main():
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--threads", default="8", help=argparse.SUPPRESS)
     ap.add_argument("--no-pipeline", action="store_true",
-                    help="skip the secondary encode_ahead measurement (`value` is the plain "
-                         "trainer loop either way)")
+                    help="with --full: skip the secondary encode_ahead measurement (`value` is the "
+                         "plain trainer loop either way)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise RCCL and run the gradient all-reducer even with one rank "
                          "(exercises the N>1 code path on a 1-GPU box)")
@@ -887,6 +1064,8 @@ def main():
         tmax = torch.tensor([elapsed], device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, losses[-1], policy)
 
     if sim:
         if rank == 0:
@@ -903,61 +1082,46 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- beside it: the same steps with the optional policy.encode_ahead() API (the frozen
-    # trunks of batch k+1 issued before batch k's update is enqueued), same step count
-    ahead_ms = None
-    if pipeline:
-        run_steps(3, ahead=True)  # warms the run-ahead path (its graphs live on the side streams)
-        sync()
-        t1 = time.perf_counter()
-        run_steps(args.steps, ahead=True)
-        sync()
-        ahead_ms = 1e3 * (time.perf_counter() - t1) / args.steps
-        if use_dist:
-            tm = torch.tensor([ahead_ms], device=dev)
-            dist.all_reduce(tm, op=dist.ReduceOp.MAX)
-            ahead_ms = tm.item()
-        log(f"with encode_ahead: {ahead_ms:.3f} ms/step")
+    if args.full:
+        # ---- beside it: the same steps with the optional policy.encode_ahead() API (the frozen
+        # trunks of batch k+1 issued before batch k's update is enqueued), same step count
+        ahead_ms = None
+        if pipeline:
+            run_steps(3, ahead=True)  # warms the run-ahead path (its graphs live on the side streams)
+            sync()
+            t1 = time.perf_counter()
+            run_steps(args.steps, ahead=True)
+            sync()
+            ahead_ms = 1e3 * (time.perf_counter() - t1) / args.steps
+            if use_dist:
+                tm = torch.tensor([ahead_ms], device=dev)
+                dist.all_reduce(tm, op=dist.ReduceOp.MAX)
+                ahead_ms = tm.item()
+            log(f"with encode_ahead: {ahead_ms:.3f} ms/step")
 
-    # ---- dominant-kernel attribution: separate, untimed-for-throughput pass
-    conv = conv_kernel_time(policy, batch[0], dev)
-    # secondary figure: forward-only act() under no_grad in eval mode
-    policy.eval()
-    h0 = torch.zeros(args.num_envs, 2, 512, device=dev)
-    with torch.no_grad():
-        for _ in range(3):
-            policy.act(batch[0], h0, batch[1], batch[2], deterministic=True)
-        sync()
-        ta = time.perf_counter()
-        for _ in range(args.steps):
-            policy.act(batch[0], h0, batch[1], batch[2], deterministic=True)
-        sync()
-        act_s = (time.perf_counter() - ta) / args.steps
-    act_small = act_latency(policy, batch, dev) if rank == 0 else {}
-    policy.train()
+        # ---- dominant-kernel attribution: separate, untimed-for-throughput pass
+        conv = conv_kernel_time(policy, batch[0], dev)
+        # secondary figure: forward-only act() under no_grad in eval mode
+        policy.eval()
+        h0 = torch.zeros(args.num_envs, 2, 512, device=dev)
+        with torch.no_grad():
+            for _ in range(3):
+                policy.act(batch[0], h0, batch[1], batch[2], deterministic=True)
+            sync()
+            ta = time.perf_counter()
+            for _ in range(args.steps):
+                policy.act(batch[0], h0, batch[1], batch[2], deterministic=True)
+            sync()
+            act_s = (time.perf_counter() - ta) / args.steps
+        act_small = act_latency(policy, batch, dev) if rank == 0 else {}
+        policy.train()
 
     if rank == 0:
         ms = 1e3 * elapsed / args.steps
         value = args.num_envs * world * args.steps / elapsed
-        # the attributed launches are the forward convolutions of the two trunks (in the
-        # trainable-encoder variant the data-gradient launches are the same kernel again)
-        conv_flop = CONV_GFLOP_PER_ENV * 1e9 * args.num_envs
         step_gflop = CMA_FWD_BWD_FROZEN_GFLOP
         if args.trainable_encoders:
             step_gflop += 2 * CONV_GFLOP_PER_ENV - STEM_GFLOP_PER_ENV
-        conv_ms, n_conv = conv["conv_ms"], conv["n"]
-        ok = conv["reason"] is None
-        achieved = conv_flop / (conv_ms * 1e-3) / 1e12 if ok else None
-        floor_rate = conv_flop / (conv["floor_ms"] * 1e-3) / 1e12 if ok else None
-        # per kernel family, from the library's own dispatch record (vlnce_conv2d_last_path)
-        fam = {0: "fp32_mfma", 1: "bf16_planes_x3", 2: "bf16_planes_p3", 3: "bf16_planes_m3"}
-        paths = {fam.get(k, str(k)): v for k, v in conv["by_path"].items()}
-        bf = [v for k, v in paths.items() if k.startswith("bf16")]
-        bf_ms, bf_flop = sum(v["ms"] for v in bf), sum(v["flop"] for v in bf)
-        f32 = paths.get("fp32_mfma", {"ms": 0.0, "flop": 0.0, "launches": 0})
-
-        def tf(v):
-            return round(v["flop"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else None
 
         line = {
             "metric": "policy-steps/sec (fwd+bwd)", "value": round(value, 1),
@@ -981,131 +1145,25 @@ def main():
                                                   "as base_il_trainer.py:176-180",
                        "loss_first_last_timed_step": [round(timed_losses[0], 5),
                                                       round(timed_losses[-1], 5)],
-                       "whole_step_tflops": round(step_gflop * value / 1e3, 2),
-                       "encode_ahead_ms_per_step": round(ahead_ms, 3) if ahead_ms else None,
-                       "encode_ahead_steps_per_sec": (
-                           round(1e3 * args.num_envs * world / ahead_ms, 1) if ahead_ms else None),
-                       "encode_ahead_is": "optional API policy.encode_ahead(obs): the frozen "
-                                          "trunks of the next batch issued on side streams before "
-                                          "this batch's update; same results "
-                                          "(tests/test_policy_gpu.py::test_encode_ahead_pipeline_"
-                                          "equals_plain_loop); NOT what `value` measures",
-                       "act_fwd_only_eval_steps_per_sec_per_gpu": round(args.num_envs / act_s, 1),
-                       "act_latency_ms_by_num_envs": act_small},
-            "roofline": {"schema": 3,
-                         "schema_is": "3 (round 6): the plane kernels issue `bf16_pipe."
-                                      "hw_flops_per_algorithmic_flop` 16-bit MFMA FLOPs per fp32 FLOP "
-                                      "(3 with fp16 planes, 6 with bf16 planes) and the per-launch "
-                                      "floor prices that count; 2 (round 5): `frac` / `peak` = the "
-                                      "per-launch max(HBM, MFMA) floor, the fp32-MFMA-peak figure "
-                                      "under `fp32_mfma_peak`; 1 (rounds 1-4): frac = achieved / fp32 "
-                                      "MFMA peak",
-                         "bound": "mfma",
-                         "kernel": "conv2d fwd of the two visual trunks: conv_p3_kernel (stride-1 "
-                                   "KxK: A transformed once per workgroup into an LDS patch, B "
-                                   "fragments from L2), conv_u3_kernel (wide 1x1: no producer "
-                                   "waves, the matrix waves transform the next K-chunk between "
-                                   "their MFMAs), conv_s3_kernel (short-K 1x1 expansions: whole K "
-                                   "resident, tile n+1's loads under tile n's stores), "
-                                   "conv_x3_kernel (the other 1x1 / strided: im2col K-tiles through "
-                                   "LDS, 8 producer + 8 matrix waves), conv_m3_kernel (small "
-                                   "launches -- the depth trunk: A fragments straight from global "
-                                   "memory, reduction split over a workgroup's waves) and "
-                                   "stem7_kernel (the 7x7/s2 RGB stem straight from the frames); "
-                                   "all six: fp32 operands "
-                                   + ("split into fp16 planes (activations a1 + a2, weights b1 + b2, "
-                                      "11 + 11 mantissa bits each), 3 x v_mfma_f32_32x32x16_f16 "
-                                      "(a1 b1 + a1 b2 + a2 b1) per 32x32x16 block"
-                                      if plane_products() == 3 else
-                                      "split exactly into 3 bf16 planes, 6 x "
-                                      "v_mfma_f32_32x32x16_bf16 per 32x32x16 block")
-                                   + ", fp32 accumulate, "
-                                   "train-mode BatchNorm column sums taken in the epilogue; "
-                                   "igemm_kernel (v_mfma_f32_32x32x2_f32) for the depth stem and "
-                                   "the handful-of-tiles layers",
-                         "achieved": round(achieved, 2) if ok else None,
-                         "peak": round(floor_rate, 2) if ok else None, "unit": "TFLOP/s",
-                         "frac": round(conv["floor_ms"] / conv_ms, 4) if ok else None,
-                         "peak_is": "the algorithmic fp32 rate these launches would reach if EACH sat "
-                                    "on its own hardware roofline, max(algorithmic bytes / achievable "
-                                    "HBM rate, instruction FLOPs / peak of the pipe it runs on) -- "
-                                    "`per_launch_floor` below has the terms; frac = achieved / peak = "
-                                    "floor_ms / kernel_ms_per_step.  The same `achieved` against the "
-                                    "fp32 MFMA peak (the reference arithmetic's roofline, which the "
-                                    "bf16-plane kernels can exceed) is `fp32_mfma_peak`; the hardware "
-                                    "FLOPs of the bf16-plane launches against their pipe `bf16_pipe`",
-                         "fp32_mfma_peak": {"peak": FP32_MFMA_PEAK_TFLOPS,
-                                            "frac": (round(achieved / FP32_MFMA_PEAK_TFLOPS, 4)
-                                                     if ok else None)},
-                         "bf16_pipe": {"instruction": ("v_mfma_f32_32x32x16_f16" if plane_products() == 3
-                                                       else "v_mfma_f32_32x32x16_bf16"),
-                                       "hw_flops_per_algorithmic_flop": plane_products(),
-                                       "peak": BF16_MFMA_PEAK_TFLOPS,
-                                       "launches": sum(v["launches"] for v in bf),
-                                       "kernel_ms_per_step": round(bf_ms, 3),
-                                       "achieved_algorithmic_tflops": (
-                                           round(bf_flop / (bf_ms * 1e-3) / 1e12, 2) if bf_ms else None),
-                                       "frac": (round(plane_products() * bf_flop / (bf_ms * 1e-3) / 1e12
-                                                      / BF16_MFMA_PEAK_TFLOPS, 4) if bf_ms and ok
-                                                else None),
-                                       "by_kernel": {k: {"launches": v["launches"],
-                                                         "ms": round(v["ms"], 3), "tflops": tf(v)}
-                                                     for k, v in paths.items() if k.startswith("bf16")}},
-                         "fp32_mfma": {"instruction": "v_mfma_f32_32x32x2_f32",
-                                       "peak": FP32_MFMA_PEAK_TFLOPS, "launches": f32["launches"],
-                                       "kernel_ms_per_step": round(f32["ms"], 3),
-                                       "achieved_tflops": tf(f32),
-                                       "frac": (round(tf(f32) / FP32_MFMA_PEAK_TFLOPS, 4)
-                                                if f32["ms"] and ok else None)},
-                         "flop_check": {"per_launch_geometry_gflop": round(conv["flop"] / 1e9, 2),
-                                        "survey_a3_gflop": round(conv_flop / 1e9, 2)},
-                         "arithmetic": (
-                             "fp32-class: a = a1 + a2 with a1 = fp16(a), a2 = fp16((a - a1) 2^11) / 2^11 "
-                             "(11 + 11 mantissa bits and the sign of a2, residual <= 2^-22 |a|), the "
-                             "same for the weights; a1 b1 + a1 b2 + a2 b1 accumulated in fp32 at the "
-                             "common scale 2^11 (dropped a2 b2 <= 2^-22); against an fp64 convolution "
-                             "as close as the six-product bf16 form (half as many fp32 accumulator "
-                             "updates; tests/test_kernels_gpu.py::test_conv_p3_matches_fp64_better_"
-                             "than_1e_6 holds both to 1e-6 rms); |x| < 65504, |w| < 32; "
-                             "VLNCE_CONV_MATH=bf16 selects three bf16 planes / six products, =f32 the "
-                             "fp32-MFMA kernel everywhere" if plane_products() == 3 else
-                             "fp32-class: operands are represented exactly by three bf16 "
-                             "planes (round-to-nearest split), products are exact, six of "
-                             "the nine are kept (dropped <= 2^-26 relative), accumulation "
-                             "is fp32; measured relative rms error vs an fp64 convolution "
-                             "1.6-2.8x torch's own fp32 convolution on the same operands "
-                             "(profiles/archive/r03_e_conv_accuracy_*.txt); VLNCE_CONV_MATH=f32 "
-                             "selects the fp32-MFMA kernel everywhere"),
-                         "per_launch_floor": {
-                             "what": "sum over the conv launches of max(algorithmic bytes / "
-                                     "achievable HBM rate, instruction FLOPs / the peak of the pipe "
-                                     "the launch runs on): the time the launches would take if "
-                                     "each sat on its own roofline; hbm_bound = the launches whose "
-                                     "HBM term is the larger one",
-                             "hbm_achievable_TBps": HBM_ACHIEVABLE_TBS, "hbm_peak_TBps": HBM_PEAK_TBS,
-                             "floor_ms": round(conv["floor_ms"], 3),
-                             "frac": round(conv["floor_ms"] / conv_ms, 4) if ok else None,
-                             "algorithmic_GB": round(conv["bytes"] / 1e9, 3),
-                             "hbm_bound": {"launches": conv["hbm_bound_n"],
-                                           "ms": round(conv["hbm_bound_ms"], 3),
-                                           "floor_ms": round(conv["hbm_floor_ms"], 3),
-                                           "achieved_TBps": (round(
-                                               conv["hbm_floor_ms"] * HBM_ACHIEVABLE_TBS
-                                               / conv["hbm_bound_ms"], 2)
-                                               if conv["hbm_bound_ms"] > 0 else None)}},
-                         "launches_per_step": n_conv,
-                         "avg_launch_ms": round(conv_ms / max(n_conv, 1), 4),
-                         "kernel_ms_per_step": round(conv_ms, 3),
-                         "eager_single_stream_trunks_ms": round(conv["eager_trunks_ms"], 3),
-                         "timing": "HIP events per launch behind a device-side backlog "
-                                   "(GPU-paced), empty-pair cost subtracted, min of 3 passes",
-                         "invalid_reason": conv["reason"],
-                         "traffic": pmc_traffic(n_conv)},
+                       "whole_step_tflops": round(step_gflop * value / 1e3, 2)},
         }
+        if args.full:
+            line["config"].update({
+                "encode_ahead_ms_per_step": round(ahead_ms, 3) if ahead_ms else None,
+                "encode_ahead_steps_per_sec": (
+                    round(1e3 * args.num_envs * world / ahead_ms, 1) if ahead_ms else None),
+                "encode_ahead_is": "optional API policy.encode_ahead(obs): the frozen "
+                                   "trunks of the next batch issued on side streams before "
+                                   "this batch's update; same results "
+                                   "(tests/test_policy_gpu.py::test_encode_ahead_pipeline_"
+                                   "equals_plain_loop); NOT what `value` measures",
+                "act_fwd_only_eval_steps_per_sec_per_gpu": round(args.num_envs / act_s, 1),
+                "act_latency_ms_by_num_envs": act_small})
+            line["roofline"] = cma_roofline(conv, args.num_envs)
         line.update(exchange_fields(exchange))
-        if world == 1 and not args.no_f32_compare and "VLNCE_CONV_MATH" not in os.environ:
+        if world == 1 and args.full and not args.no_f32_compare and "VLNCE_CONV_MATH" not in os.environ:
             line["config"]["fp32_mfma_only"] = f32_mfma_compare(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.num_envs, args.hw, args.tokens)
         final = json.dumps(line)
     if use_dist:

@@ -376,6 +376,62 @@ def run_case(policy, case, obs, prev, masks, extra, update_fn=None, aux=None, pp
     return {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
 
 
+PART_BYTES = 900 << 10   # every fixture file stays below 1 MiB
+
+
+def _compressed_size(a):
+    import io
+    buf = io.BytesIO()
+    np.savez_compressed(buf, a=a)
+    return buf.tell()
+
+
+def save_npz(path, blob):
+    """np.savez_compressed of `blob`, spread over `path` and `<stem>.part<i>.npz` beside it so that
+    no file exceeds PART_BYTES; an array too large for one file is cut along its first axis into
+    `key#0`, `key#1`, ... .  load_npz reassembles exactly what was given."""
+    pieces = []   # (compressed size, key, array)
+    for k, v in blob.items():
+        v = np.asarray(v)
+        size = _compressed_size(v)
+        if size <= PART_BYTES:
+            pieces.append((size, k, v))
+            continue
+        for i, c in enumerate(np.array_split(v, -(-size // PART_BYTES) + 1)):
+            pieces.append((_compressed_size(c), f"{k}#{i}", c))
+    parts = []    # first fit, largest first
+    for size, k, v in sorted(pieces, key=lambda p: -p[0]):
+        for p in parts:
+            if p[0] + size <= PART_BYTES:
+                p[0] += size
+                p[1][k] = v
+                break
+        else:
+            parts.append([size, {k: v}])
+    stem = path[:-len(".npz")]
+    for i, (_, arrays) in enumerate(parts):
+        np.savez_compressed(path if i == 0 else f"{stem}.part{i}.npz", **arrays)
+
+
+def load_npz(path):
+    """{key: array} of a fixture written by save_npz (or by a plain np.savez_compressed)."""
+    import glob
+    import re
+    files = [path] + sorted(glob.glob(glob.escape(path[:-len(".npz")]) + ".part*.npz"))
+    out, cut = {}, {}
+    for f in files:
+        z = np.load(f, allow_pickle=False)
+        for k in z.files:
+            m = re.fullmatch(r"(.*)#(\d+)", k)
+            if m:
+                cut.setdefault(m.group(1), {})[int(m.group(2))] = z[k]
+            else:
+                out[k] = z[k]
+    for k, chunks in cut.items():
+        out[k] = np.concatenate([chunks[i] for i in range(len(chunks))])
+    return out
+
+
 def save_case(path, case_name, obs, prev, masks, extra, outputs):
     blob = {}
     if CASES.get(case_name, {}).get("outputs_only"):
@@ -384,7 +440,7 @@ def save_case(path, case_name, obs, prev, masks, extra, outputs):
         # regenerate from the seed)
         blob.update(to_numpy_tree({k: v for k, v in extra.items() if k.startswith("act_")},
                                   "in/extra/"))
-        np.savez_compressed(path, **blob)
+        save_npz(path, blob)
         return
     ins = dict(obs=dict(obs), masks=masks, extra=extra)
     ins["prev"] = prev if isinstance(prev, dict) else {"_": prev}
@@ -393,20 +449,20 @@ def save_case(path, case_name, obs, prev, masks, extra, outputs):
             ins["obs"][k] = ins["obs"][k].to(torch.uint8)  # integer-valued: exact
     blob.update(to_numpy_tree(ins, "in/"))
     blob.update(to_numpy_tree(outputs, "out/"))
-    np.savez_compressed(path, **blob)
+    save_npz(path, blob)
 
 
 def load_case(path, device="cpu"):
     """(obs, prev, masks, extra, expected outputs); an outputs-only fixture regenerates its inputs
     from the seed (build_inputs of the case named like the file)."""
-    z = np.load(path, allow_pickle=False)
+    z = load_npz(path)
     import os
     name = os.path.splitext(os.path.basename(path))[0]
     if CASES.get(name, {}).get("outputs_only"):
         outs = {k[4:]: (z[k] if z[k].dtype.kind in "US" else torch.from_numpy(z[k]))
-                for k in z.files if k.startswith("out/")}
+                for k in z if k.startswith("out/")}
         obs, prev, masks, extra = build_inputs(CASES[name])
-        for k in z.files:
+        for k in z:
             if k.startswith("in/extra/"):
                 extra[k[9:]] = torch.from_numpy(z[k])
         mv = lambda t: t.to(device) if isinstance(t, torch.Tensor) else t  # noqa: E731
@@ -414,7 +470,7 @@ def load_case(path, device="cpu"):
                 {k: mv(v) for k, v in extra.items()}, outs)
     obs, prev, extra, outs = {}, {}, {}, {}
     masks = None
-    for k in z.files:
+    for k in z:
         v = z[k]
         if k.startswith("out/"):
             outs[k[4:]] = v if v.dtype.kind in "US" else torch.from_numpy(v)
