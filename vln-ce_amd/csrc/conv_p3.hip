@@ -30,8 +30,9 @@
 // A workgroup is 8 matrix waves (two per SIMD taking turns on the matrix pipe) + 4 producer waves
 // (one per SIMD), 168 VGPRs each, one workgroup per CU, persistent over a strided tile list; the
 // hand-over is per patch buffer (two of them) through LDS counters as in conv_x3_kernel.
+// This file also holds the weight packer and the router p3_try_launch, which hands the 1x1 layers
+// it finds eligible to conv_u3_kernel (conv_u3.hip) and conv_s3_kernel (conv_s3.hip).
 #include "igemm_shared.h"
-#include <type_traits>
 
 using namespace vlnce_detail;
 
@@ -41,16 +42,6 @@ namespace {
 // bytes per patch row: Planes<MATH>::ROW (208 = 13 x 16 B / 144 = 9 x 16 B: consecutive rows are
 // conflict-free for ds_read_b128)
 constexpr int P3_PRODUCERS = 4;  // producer waves
-#ifndef U3_B_AHEAD_64
-#define U3_B_AHEAD_64 2    // conv_u3_kernel: B fragments requested a chunk ahead (see BA in the kernel)
-#endif
-#ifndef U3_B_AHEAD_128
-#define U3_B_AHEAD_128 1
-#endif
-#ifndef U3_RAW_BATCH
-#define U3_RAW_BATCH 1   // conv_u3_kernel: raw-row chunks per request burst (2: the round-6 experiment below)
-#endif
-constexpr int U3_MAX_CIN = 4096;   // conv_u3_kernel: input channels whose prologue vectors fit its LDS
 // patch rows the KxK producers address: 12 row groups of 32 (3 items of 128), their byte offsets in
 // twelve registers.  (Round 6, measured and dropped: with the 144-byte rows of the fp16 planes the LDS
 // would hold 568 rows, i.e. 256-row tiles on 64x64 maps -- but 16 offsets in registers pushed the
@@ -64,24 +55,8 @@ constexpr int U3_MAX_CIN = 4096;   // conv_u3_kernel: input channels whose prolo
 // stay on 128x64 tiles (one accumulator block per wave), 185-195 TF/s against 300-330 TF/s for the
 // 128- to 512-channel layers.)
 constexpr int P3_MAX_ROWS = 384;
-#ifndef P3_DENSE_VEC_GLOBAL   // (A/B switch: the KxK producers' prologue vectors as per-chunk global loads)
-#define P3_DENSE_VEC_LDS 1
-#else
-#define P3_DENSE_VEC_LDS 0
-#endif
-#ifndef P3_MPRIO
-#define P3_MPRIO 1   // s_setprio of the matrix waves
-#endif
-#ifndef P3_PPRIO
-#define P3_PPRIO 2   // s_setprio of the producer waves: measured, a producer-bound layer
-                     // (3x3 64->64 at 64x64) runs 140 -> 119 us when the producers win the issue port
-#endif
 
 enum { P3_GATHER = 0, P3_DENSE = 1 };
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 // Wait for an LDS counter of the hand-over.  Waits are between the waves of ONE workgroup, i.e.
 // microseconds; a protocol bug must become a launch error, not a hung GPU: after ~0.2 s of
@@ -94,17 +69,6 @@ __device__ __forceinline__ void p3_wait(const int* flag, int need) {
     if (spins > (1 << 22)) __builtin_trap();
   }
   asm volatile("" ::: "memory");
-}
-
-// x (4 consecutive k of one patch row) -> the A planes' 8-byte words, round-to-nearest split
-template <int MATH>
-__device__ __forceinline__ void p3_split_store(f32x4 x, char* row_ptr) {
-  constexpr int NA = Planes<MATH>::NA;
-  unsigned w0[NA], w1[NA];
-  split_pair<MATH>(x[0], x[1], w0);
-  split_pair<MATH>(x[2], x[3], w1);
-#pragma unroll
-  for (int q = 0; q < NA; ++q) *reinterpret_cast<u32x2*>(row_ptr + q * 64) = u32x2{w0[q], w1[q]};
 }
 
 template <int BM, int BN, int WM, int WN, int DUAL, int MODE, int MATH>
@@ -169,7 +133,7 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
   };
 
   if (tid < 4) pfull[tid] = 0;
-  if constexpr (MODE == P3_DENSE && P3_DENSE_VEC_LDS) {
+  if constexpr (MODE == P3_DENSE) {
     const bool pro = p.in_scale != nullptr;
     for (int ch = tid; ch < p.Cin; ch += (MATRIX + P3_PRODUCERS) * 64) {
       vlds[ch] = pro ? p.in_scale[ch] : 1.f;
@@ -181,6 +145,9 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
 
   if (wave >= MATRIX) {
     // ================================================================ producer waves
+    // producer waves above the matrix waves: measured, a producer-bound layer (3x3 64->64 at
+    // 64x64) runs 140 -> 119 us when the producers win the issue port
+    constexpr int P3_PPRIO = 2;
     __builtin_amdgcn_s_setprio(P3_PPRIO);
     const int ptid = tid - MATRIX * 64;
     const int lrow = ptid >> 3;          // row inside a 32-row pass
@@ -252,10 +219,7 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
       }
       p3_split_store<MATH>(v, dst);
     };
-#ifdef P3_DBG_TIME
-    long long d_wait = 0, d_vmw = 0, d_tr = 0, d_ld = 0;
-    const long long d_t0 = clock64();
-#endif
+    DBG_T(long long d_wait = 0, d_vmw = 0, d_tr = 0, d_ld = 0; const long long d_t0 = clock64();)
 
     if constexpr (MODE == P3_GATHER) {
       // ---- 1x1 convolutions: patch row = output pixel, BM / 32 row groups per chunk, all of a
@@ -324,13 +288,9 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
         char* const buf = xsm + (g & 1) * pbuf + (part * NPI * 32 + lrow) * P3_ROW + lk4 * 2;
         if (part == 0) {
           next_vec(s_c + 1);
-#ifdef P3_DBG_TIME
-          const long long d_a = clock64();
-#endif
+          DBG_T(const long long d_a = clock64();)
           p3_wait(pempty + (g & 1), MATRIX * (g >> 1));  // chunk g-2 has been read
-#ifdef P3_DBG_TIME
-          d_wait += clock64() - d_a;
-#endif
+          DBG_T(d_wait += clock64() - d_a;)
         }
 #pragma unroll
         for (int i = 0; i < NPI; ++i) {
@@ -462,38 +422,25 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
       auto stash = [&](const Staged& s) {
         char* const buf = xsm + (s_h & 1) * pbuf + lk4 * 2;
         if (s_part == 0) {
-#if P3_DENSE_VEC_LDS
           const float* const vp = vlds + s_c * 32 + lk4;   // this chunk's vectors (LDS, staged once)
           cur.s = *reinterpret_cast<const f32x4*>(vp);
           cur.t = *reinterpret_cast<const f32x4*>(vp + p.Cin);
           cur.c = *reinterpret_cast<const f32x4*>(vp + 2 * p.Cin);
-#else
-          next_vec(s_c + 1);
-#endif
-#ifdef P3_DBG_TIME
-          const long long d_a = clock64();
-#endif
+          DBG_T(const long long d_a = clock64();)
           p3_wait(pempty + (s_h & 1), MATRIX * (s_h >> 1));  // chunk h-2 has been read
-#ifdef P3_DBG_TIME
-          d_wait += clock64() - d_a;
-#endif
+          DBG_T(d_wait += clock64() - d_a;)
         }
-#ifdef P3_DBG_TIME
-        const long long d_b = clock64();
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // this item's 4 loads (4 newer ones fly)
-        const long long d_c = clock64();
-        d_vmw += d_c - d_b;
-#endif
+        DBG_T(const long long d_b = clock64();
+              asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // this item's 4 loads (4 newer ones fly)
+              const long long d_c = clock64();
+              d_vmw += d_c - d_b;)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int j = (s_part * 4 + i) * 32 + lrow;
           if (j < p.p3_rows)  // (the last item may reach past the rows the buffer holds)
             transform_store(s.a[i], zero4, (s.ok >> i) & 1u, buf + j * P3_ROW, nullptr);
         }
-#ifdef P3_DBG_TIME
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        d_tr += clock64() - d_c;
-#endif
+        DBG_T(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); d_tr += clock64() - d_c;)
         if (++s_part == s_nparts) {
           if (lane == 0) x3_signal(pfull + (s_h & 1));  // (in LDS order behind this wave's writes)
           s_part = 0;
@@ -506,18 +453,11 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
       };
       l_setup(0);
       s_setup(0);
-#if !P3_DENSE_VEC_LDS
-      load_vec(nxt, 0);
-#endif
       load(st[0]);
       while (s_round < my_tiles) {
-#ifdef P3_DBG_TIME
-        const long long d_l = clock64();
-#endif
+        DBG_T(const long long d_l = clock64();)
         load(st[1]);
-#ifdef P3_DBG_TIME
-        d_ld += clock64() - d_l;
-#endif
+        DBG_T(d_ld += clock64() - d_l;)
         stash(st[0]);
         if (s_round < my_tiles) {
           load(st[0]);
@@ -525,7 +465,7 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
         }
       }
     }
-#ifdef P3_DBG_TIME
+#ifdef VLNCE_DBG_TIME
     if (blockIdx.x == 8 && ptid == 0)
       printf("p3 producer: total %lld cycles, waiting for the matrix waves %lld; KxK form: waiting for "
              "loads %lld, transform + LDS writes %lld, issuing every other item's loads %lld\n",
@@ -600,11 +540,9 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
 
     // the SIMD's VALU issue port is shared with the producer wave: the MFMAs must win it the
     // moment the matrix pipe frees up
+    constexpr int P3_MPRIO = 1;   // (the producer waves run at 2, see there)
     __builtin_amdgcn_s_setprio(P3_MPRIO);
-#ifdef P3_DBG_TIME
-    long long d_pf = 0, d_vm = 0, d_lg = 0;
-    const long long d_t0 = clock64(), d_w0 = wall_clock64();
-#endif
+    DBG_T(long long d_pf = 0, d_vm = 0, d_lg = 0; const long long d_t0 = clock64(), d_w0 = wall_clock64();)
     int h = 0;
     int vb[NT], vbn[NT];
     WaveBn<NT> wbn;   // BatchNorm finished in this launch (p.bn): the wave's running column sums
@@ -657,13 +595,9 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
 
       int ks3 = 0;  // byte offset of the current k-slab pair inside an n-block's fragments
       for (int c = 0; c < NC; ++c, ++h) {
-#ifdef P3_DBG_TIME
-        const long long d_a = clock64();
-#endif
+        DBG_T(const long long d_a = clock64();)
         p3_wait(pfull + (h & 1), P3_PRODUCERS * ((h >> 1) + 1));
-#ifdef P3_DBG_TIME
-        d_pf += clock64() - d_a;
-#endif
+        DBG_T(d_pf += clock64() - d_a;)
         const int bufoff = (h & 1) * pbuf;
         int tr = 0, tq = 0;
         for (int t = 0; t < T; ++t) {
@@ -679,17 +613,14 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
             for (int q = 0; q < NA; ++q)
               fa[i][q] = *reinterpret_cast<const bf16x8*>(abase + a_row[i] + q * 64);
           __builtin_amdgcn_sched_barrier(0);
-#ifdef P3_DBG_TIME
-          {
+          DBG_T({
             const long long d_0 = clock64();
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(B_LDS ? 0 : NT * 3) : "memory");
             const long long d_1 = clock64();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             d_vm += d_1 - d_0;
             d_lg += clock64() - d_1;
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#endif
+          } __builtin_amdgcn_sched_barrier(0);)
           mma(b0);
           __builtin_amdgcn_sched_barrier(0);
           // ---- k-slab 1: B fragments in b1; b0 <- the next step's (or the next tile's first)
@@ -745,7 +676,7 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
                             rsrc_c, rsrc_r, false);
     }
     __builtin_amdgcn_s_setprio(0);
-#ifdef P3_DBG_TIME
+#ifdef VLNCE_DBG_TIME
     if (blockIdx.x == 8 && (tid == 0 || tid == 64 * (MATRIX - 1))) {
       const long long c = clock64() - d_t0, w = wall_clock64() - d_w0;
       printf("p3 matrix wave %d: tiles %d chunks %d taps %d: total %lld cycles = %lld ticks of 100 MHz "
@@ -755,845 +686,6 @@ __global__ __launch_bounds__((WM * WN + P3_PRODUCERS) * 64) void conv_p3_kernel(
 #endif
   }
 #endif
-}
-
-// ====================================================================================
-// conv_u3_kernel: 1x1 convolutions with NO producer waves.
-//
-// What the in-kernel timers of conv_p3_kernel / conv_x3_kernel show for the 1x1 layers (60 % of
-// the trunks' convolution time): a dedicated producer wave next to two MFMA-issuing waves of its
-// SIMD gets one instruction in 15-20 cycles -- it has no second wave to hide its own dependency
-// and LDS latencies behind, and the matrix waves own the issue port -- so the matrix waves wait
-// for the patch.  Here every wave does both jobs, and the compiler interleaves them in ONE
-// instruction stream: 8 waves (two per SIMD, 256 VGPRs each), wave w owns output columns
-// [32 w, 32 w + 32) of a BM x 256 tile for ALL BM rows (MT = BM / 32 MFMA blocks: a B fragment
-// fetched from L2 feeds MT MFMAs), and, between the MFMAs of K-chunk g, transforms its 1/8 share
-// of the rows of K-chunk g + 1 (BatchNorm + ReLU prologue, block end, three-way bf16 split) into
-// the other patch buffer.  One raw s_barrier per K-chunk (48 MFMAs per wave) swaps the buffers;
-// raw A rows are fetched two chunks ahead into registers, B fragments one k-slab ahead.
-// (Round 6, measured and dropped: a ring of three / four raw-row sets -- inside a trunk the rows come
-// from HBM, not from the Infinity Cache scripts/convbench.py keeps them in (--rotate: 1024 -> 256 block
-// end 48 us cache-hot, 69 us from HBM) -- is 5-19 % SLOWER on the 128-row single-input form, cache-hot
-// and from HBM alike, and changes nothing on the 64-row forms: profiles/r06_i_*.)
-// WAVES = 8: two waves per SIMD, 256 registers each, a wave owns BM x 32 outputs;
-// WAVES = 4: ONE wave per SIMD with the whole 512-register file, a wave owns BM x 64 outputs and
-// double-buffers its A fragments (no partner wave to hide LDS latency behind).
-// LINEAR: stride 1 (input pixel = output pixel).  A compile-time flag: as a runtime one the
-// strided path's division constants stayed live through the chunk loop, were spilled, and were
-// reloaded from scratch behind every chunk's MFMAs -- each reload followed by an
-// s_waitcnt vmcnt(0) that drained the wave's whole prefetch queue (profiles/archive/r03_n_*).
-// DUAL: 0 = one input; 1 = block end with an identity skip (second input added as is); 2 = block
-// end whose skip path has its own BatchNorm.  Compile-time: the identity form carries half the
-// prologue vectors and its chunk body has no branch.
-template <int BM, int DUAL, int WAVES, int LINEAR, int MATH>
-__global__ __launch_bounds__(WAVES * 64) void conv_u3_kernel(IgemmParams p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  typedef Planes<MATH> PL;
-  constexpr int P3_ROW = PL::ROW, NA = PL::NA;
-  constexpr int BN = 256, MT = BM / 32, NT = 8 / WAVES;
-  constexpr int RG = WAVES * 8;                  // rows per group of the transform's thread map
-  constexpr int NPT = BM / RG;                   // float4 of a K-chunk's A rows per thread
-  constexpr bool ADB = WAVES == 4;               // A fragments double-buffered across the k-slabs
-  static_assert(NPT >= 1 && MT >= 1 && (WAVES == 8 || WAVES == 4), "tile");
-  constexpr int PBUF = BM * P3_ROW;
-  extern __shared__ __attribute__((aligned(16))) char xsm[];  // [2][PBUF] + prologue vectors [NV][Cin]
-  // The prologue vectors (scale / shift / centre per input channel, twice for a skip path with its
-  // own BatchNorm) live in LDS for the whole launch (round 6).  As per-chunk global loads into a
-  // `cur` / `nxt` register pair they cost 24-48 VGPRs (the 128-row instances spilled) and sat in
-  // the wave's one in-order vmcnt queue between the raw-row and B-fragment prefetches.
-  constexpr int NV = DUAL == 2 ? 6 : 3;
-  float* const vlds = reinterpret_cast<float*>(xsm + 2 * PBUF);
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5;
-  const int l31 = lane & 31;
-  const int NC = p.Cin / 32;
-  const int HoWo = p.Ho * p.Wo;
-  const int trow = tid >> 3;          // this thread's row inside a group of RG rows
-  const int lk4 = (tid & 7) * 4;
-
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int my_tiles = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  auto tile_of = [&](int round, int& m0, int& n0) {
-    const int v = blockIdx.x + round * gridDim.x;
-    const int q = ntiles >> 3, r = ntiles & 7, xcd = v & 7, idx = v >> 3;
-    const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    const int tm = tile / p.tiles_n;
-    m0 = tm * BM;
-    n0 = (tile - tm * p.tiles_n) * BN;
-  };
-  const int G = my_tiles * NC;  // K-chunks this workgroup streams
-
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char*>(reinterpret_cast<const char*>(p.A)), 0, (int)p.a_bytes, 0x00020000);
-  __amdgpu_buffer_rsrc_t rsrc_a2 = rsrc_a;
-  if constexpr (DUAL)
-    rsrc_a2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.A2)), 0, (int)p.a_bytes, 0x00020000);
-  const int KS3 = (p.K / 16) * 3072;
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char*>(reinterpret_cast<const char*>(p.Bfrag)), 0, (int)((long)p.N * p.K * 6),
-      0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<char*>(p.C), 0, (int)p.c_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_r = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char*>(reinterpret_cast<const char*>(p.residual ? p.residual : p.C)), 0,
-      (int)p.c_bytes, 0x00020000);   // (ldr == ldc: the output's extent)
-  const bool has_pro = p.in_scale != nullptr;
-  const float relu_floor = p.in_relu ? 0.f : -__builtin_huge_valf();
-  constexpr bool linear = LINEAR != 0;
-
-  // ---------------------------------------------------------------- the A side (every thread)
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  for (int ch = tid; ch < p.Cin; ch += WAVES * 64) {   // neutral vectors where there is no prologue
-    vlds[ch] = has_pro ? p.in_scale[ch] : 1.f;
-    const float t1 = has_pro ? p.in_shift[ch] : 0.f;
-    vlds[p.Cin + ch] = t1;
-    vlds[2 * p.Cin + ch] = (has_pro && p.in_center) ? p.in_center[ch] : 0.f;
-    if constexpr (DUAL == 2) {
-      vlds[3 * p.Cin + ch] = p.in2_scale[ch];
-      vlds[4 * p.Cin + ch] = t1 + p.in2_shift[ch];   // both shifts in one add
-      vlds[5 * p.Cin + ch] = p.in2_center ? p.in2_center[ch] : 0.f;
-    }
-  }
-  __syncthreads();
-  struct Raw {
-    f32x4 a[NPT];
-    f32x4 a2[DUAL ? NPT : 1];
-    unsigned ok;
-    int m0;  // first row of the tile if this workgroup writes side_out for it, else -1
-    int ci;  // first input channel of the chunk
-  };
-  int a_voff[NPT];
-  unsigned a_ok = 0;
-  int l_round = 0, l_c = 0, l_m0 = 0, l_side = 0;
-  auto setup_tile = [&](int round) {
-    int m0, n0;
-    tile_of(round, m0, n0);
-    l_m0 = m0;
-    l_side = n0 == 0;
-    a_ok = 0;
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      const int m = m0 + i * RG + trow;
-      a_voff[i] = BUF_OOB;
-      if (m < p.M) {
-        int pix = m;
-        if constexpr (!linear) {
-          const int img = m / HoWo;
-          const int rem = m - img * HoWo;
-          const int ho = rem / p.Wo;
-          pix = (img * p.H + ho * p.stride) * p.W + (rem - ho * p.Wo) * p.stride;
-        }
-        a_voff[i] = (pix * p.lda + lk4) * 4;
-        a_ok |= 1u << i;
-      }
-    }
-  };
-  auto load_raw = [&](Raw& r) {   // (branch-free; advance_raw() moves the cursor afterwards)
-    const bool live = l_round < my_tiles;
-    const int soff = l_c * 128;
-    r.ok = live ? a_ok : 0u;
-    r.m0 = l_side ? l_m0 : -1;
-    r.ci = l_c * 32;
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      const int vo = live ? a_voff[i] : BUF_OOB;
-      r.a[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, vo, soff, 0));
-      if constexpr (DUAL)
-        r.a2[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_a2, vo, soff, 0));
-    }
-  };
-  auto advance_raw = [&]() {
-    if (l_round < my_tiles && ++l_c == NC) {
-      l_c = 0;
-      if (++l_round < my_tiles) setup_tile(l_round);
-    }
-  };
-  // prologue + split of this thread's float4s of one chunk into patch buffer `buf`.  Branch-free
-  // in the single-input form (neutral vectors where the convolution has no prologue: x*1+0 and
-  // max(x, -inf) are exact), so that it shares ONE basic block with the MFMAs of the chunk and
-  // the scheduler can interleave the two.
-  auto transform = [&](const Raw& r, char* buf) {
-    struct {
-      f32x4 s, t, c, s2, t2, c2;
-    } cur;
-    const float* const vp = vlds + r.ci + lk4;
-    cur.s = *reinterpret_cast<const f32x4*>(vp);
-    cur.t = *reinterpret_cast<const f32x4*>(vp + p.Cin);
-    cur.c = *reinterpret_cast<const f32x4*>(vp + 2 * p.Cin);
-    if constexpr (DUAL == 2) {
-      cur.s2 = *reinterpret_cast<const f32x4*>(vp + 3 * p.Cin);
-      cur.t2 = *reinterpret_cast<const f32x4*>(vp + 4 * p.Cin);
-      cur.c2 = *reinterpret_cast<const f32x4*>(vp + 5 * p.Cin);
-    }
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      f32x4 v = r.a[i];
-      const bool ok = (r.ok >> i) & 1u;
-      if constexpr (DUAL) {
-        if constexpr (DUAL == 2) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            v[e] = fmaxf(fmaf(v[e] - cur.c[e], cur.s[e],
-                              fmaf(r.a2[i][e] - cur.c2[e], cur.s2[e], cur.t2[e])), relu_floor);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            v[e] = fmaxf(fmaf(v[e] - cur.c[e], cur.s[e], cur.t[e]) + r.a2[i][e], relu_floor);
-        }
-        if (!ok) v = zero4;
-        if (p.side_out != nullptr && r.m0 >= 0 && ok)
-          *reinterpret_cast<f32x4*>(p.side_out + (long)(r.m0 + i * RG + trow) * p.lda + r.ci + lk4) = v;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[e] = fmaxf(fmaf(v[e] - cur.c[e], cur.s[e], cur.t[e]), relu_floor);
-          v[e] = ok ? v[e] : 0.f;
-        }
-      }
-      p3_split_store<MATH>(v, buf + (i * RG + trow) * P3_ROW + lk4 * 2);
-    }
-  };
-
-  // ---------------------------------------------------------------- the matrix side (per wave)
-  constexpr int HM = MT / 2;  // row blocks per half (two-wave form)
-  static_assert(ADB || HM >= 1, "tile");
-  bf16x8 fa[ADB ? MT : 1][NA], fa1[ADB ? MT : 1][NA], fh0[ADB ? 1 : HM][NA], fh1[ADB ? 1 : HM][NA];
-  // BA (B fragments ahead): 0 = k-slab 1's fragments requested at the start of their chunk and the
-  // next chunk's slab-0 fragments half a chunk ahead (one slab of lead: 6 * MT MFMAs against an L2
-  // round trip); 1 = slab 1's fragments a whole chunk ahead (a second set, alternating by chunk
-  // parity); 2 = both slabs' fragments a whole chunk ahead (two more sets: the 64-row forms have
-  // the registers).  Single-input forms only: 1x1 layer list 2.219 -> 2.158 ms from HBM (1024 ->
-  // 256: 179 -> 207 TF/s); the dual forms measured 3 % SLOWER with it (the 128-row ones spill 6-8
-  // registers) and keep one slab of lead (profiles/r06_u_conv_u3_b_fragments_a_chunk_ahead.txt).
-  constexpr int BA = (ADB || DUAL != 0) ? 0 : (BM == 64 ? U3_B_AHEAD_64 : U3_B_AHEAD_128);
-  bf16x8 b0[NT][3], b1[NT][3];
-  bf16x8 b0x[BA == 2 ? NT : 1][3], b1x[BA >= 1 ? NT : 1][3];
-  f32x16 acc[MT][NT];
-  const int a_off = l31 * P3_ROW + half * 16;   // + i * 32 * P3_ROW + q * 64 + s * 32
-  auto loadB = [&](bf16x8 (&b)[NT][3], const int (&vb)[NT], int soff) {
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        b[j][q] = __builtin_bit_cast(
-            bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
-                        rsrc_b, vb[j] == BUF_OOB ? BUF_OOB : vb[j] + q * 1024, soff, 0));
-  };
-  auto readA = [&](bf16x8 (&f)[ADB ? MT : 1][NA], const char* buf, int s) {
-#pragma unroll
-    for (int i = 0; i < (ADB ? MT : 1); ++i)
-#pragma unroll
-      for (int q = 0; q < NA; ++q)
-        f[i][q] = *reinterpret_cast<const bf16x8*>(buf + a_off + i * 32 * P3_ROW + q * 64 + s * 32);
-  };
-  auto readH = [&](bf16x8 (&f)[ADB ? 1 : HM][NA], const char* buf, int s, int h) {
-#pragma unroll
-    for (int i = 0; i < (ADB ? 1 : HM); ++i)
-#pragma unroll
-      for (int q = 0; q < NA; ++q)
-        f[i][q] = *reinterpret_cast<const bf16x8*>(buf + a_off + (h * HM + i) * 32 * P3_ROW + q * 64 +
-                                                   s * 32);
-  };
-  constexpr int NP = PL::NP;
-  auto mma = [&](const bf16x8 (&f)[ADB ? MT : 1][NA], const bf16x8 (&b)[NT][3]) {
-#pragma unroll
-    for (int q = 0; q < NP; ++q)
-#pragma unroll
-      for (int i = 0; i < (ADB ? MT : 1); ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[i][j] = plane_mfma<MATH>(f[i][PL::PA[q]], b[j][PL::PB[q]], acc[i][j]);
-  };
-  auto mmaH = [&](const bf16x8 (&f)[ADB ? 1 : HM][NA], const bf16x8 (&b)[NT][3], int h) {
-#pragma unroll
-    for (int q = 0; q < NP; ++q)
-#pragma unroll
-      for (int i = 0; i < (ADB ? 1 : HM); ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[h * HM + i][j] = plane_mfma<MATH>(f[i][PL::PA[q]], b[j][PL::PB[q]], acc[h * HM + i][j]);
-  };
-  auto vb_of = [&](int n0, int (&vb)[NT]) {
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int nb = n0 / 32 + wave * NT + j;
-      vb[j] = nb * 32 < p.N ? nb * KS3 + lane * 16 : BUF_OOB;
-    }
-  };
-
-  // ---------------------------------------------------------------- prologue of the stream
-  // vector schedule: chunk k's vectors are channels (k % NC) * 32 ..; `cur` must hold chunk k's
-  // when chunk k is transformed
-  //
-  // RB = 2 (round 6, single-input forms): raw rows requested TWO chunks at a time, every second
-  // chunk.  A wave has ONE in-order vmcnt queue: the B fragments of the next k-slab (L2 hits,
-  // needed half a chunk after they are requested) queue behind the raw rows requested just before
-  // them (HBM), so every chunk waits out part of an HBM latency with one chunk of rows in flight.
-  // Two chunks per burst put twice the bytes behind each such wait, for four raw sets in
-  // registers instead of two.  Measured per layer from HBM (scripts/convbench.py --rotate 8,
-  // profiles/r06_p_conv_u3_raw_batch_ab.txt): K >= 512 layers +7...15 % (1024 -> 512: 224 -> 258
-  // TF/s), 256 -> 1024 -6 %, the 1x1 layer list 2.184 -> 2.158 ms; the dual (block-end) forms
-  // measured 1-5 % SLOWER with it and keep one chunk per request; the step is unchanged within
-  // its noise (5.44-5.49 ms of conv launches either way), and the file compiles 40 % longer:
-  // NOT the default (-DU3_RAW_BATCH=2 builds it).
-  // (Also measured and dropped: the dual forms' side_out rows stored two chunks per burst instead
-  // of every chunk -- stores count in the same queue -- block ends 2.870 -> 2.946 ms, i.e. slower:
-  // profiles/r06_s_conv_u3_side_out_store_bursts.txt.)
-  constexpr int RB = (U3_RAW_BATCH == 2 && DUAL == 0) ? 2 : 1;
-  Raw rx, ry, rz, rw;   // RB = 2: chunk j lives in set j % 4 (rx, ry, rz, rw); RB = 1: rx / ry alternate
-  setup_tile(0);
-  load_raw(rx);   // chunk 0
-  advance_raw();
-  load_raw(ry);   // chunk 1
-  advance_raw();
-  if constexpr (RB == 2) {
-    load_raw(rz);   // chunks 2, 3
-    advance_raw();
-    load_raw(rw);
-    advance_raw();
-  }
-  int m0 = 0, n0 = 0;
-  tile_of(0, m0, n0);
-  int vb[NT], vbn[NT];
-  vb_of(n0, vb);
-#pragma unroll
-  for (int j = 0; j < NT; ++j) vbn[j] = BUF_OOB;
-  if (my_tiles > 1) {
-    int m1, n1;
-    tile_of(1, m1, n1);
-    vb_of(n1, vbn);
-  }
-  loadB(b0, vb, 0);
-  if constexpr (BA >= 1) loadB(b1, vb, 3072);
-  transform(rx, xsm);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  int c = 0, round = 0, ks3 = 0;
-  WaveBn<NT> wbn;   // BatchNorm finished in this launch (p.bn): the wave's running column sums
-  wave_bn_reset(wbn);
-#ifdef P3_DBG_TIME
-  long long d_blk = 0, d_epi = 0, d_bar = 0, d_book = 0;
-  const long long d_t0 = clock64(), d_w0 = wall_clock64();
-#endif
-  // one K-chunk: MFMAs on patch (g & 1) / transform of `rn` (chunk g + 1) into patch ((g+1) & 1) /
-  // raw loads of chunk g + 2 into `rf`.  Everything up to the transform is ONE basic block.
-  auto chunk = [&](int g, Raw& rn, Raw& rf, Raw& rf2, auto pair_tag, bf16x8 (&b0c)[NT][3],
-                   bf16x8 (&b1c)[NT][3], auto& b0n, auto& b1n) {
-    constexpr bool load_pair = decltype(pair_tag)::value;   // RB = 2: this chunk ends with a request burst
-    const char* const pb = xsm + (g & 1) * PBUF;
-    char* const pn = xsm + ((g + 1) & 1) * PBUF;
-    const bool last_of_tile = c == NC - 1;
-    int vb_s0[NT];                                         // slab 0 of the next chunk
-#pragma unroll
-    for (int j = 0; j < NT; ++j) vb_s0[j] = last_of_tile ? vbn[j] : vb[j];
-    const int so_s0 = last_of_tile ? 0 : ks3 + 6144;
-#ifdef P3_DBG_TIME
-    const long long d_0 = clock64();
-#endif
-#ifdef U3_RAW_FIRST
-    if constexpr (RB == 1) load_raw(rf);
-    loadB(b1c, vb, ks3 + 3072);
-#else
-    // k-slab 1's B fragments BEFORE the raw rows of chunk g + 2: vmcnt retires in order, and the
-    // fragments (L2 hits, needed half a chunk from here) would otherwise wait out the HBM latency
-    // of rows that nobody reads before the next chunk
-    if constexpr (BA == 0) loadB(b1c, vb, ks3 + 3072);
-    if constexpr (BA == 2) loadB(b0n, vb_s0, so_s0);              // the NEXT chunk's fragments
-    if constexpr (BA >= 1) loadB(b1n, vb_s0, so_s0 + 3072);
-    if constexpr (RB == 1) load_raw(rf);
-#endif
-    if constexpr (ADB) {
-      readA(fa, pb, 0);
-      readA(fa1, pb, 1);
-      mma(fa, b0c);
-      loadB(b0n, vb_s0, so_s0);
-      mma(fa1, b1c);
-    } else {
-      // the MT row blocks in two halves with a fragment set each: the reads of one half land
-      // under the MFMAs of the other (no spare registers for a second full set)
-      readH(fh0, pb, 0, 0);
-      readH(fh1, pb, 0, 1);
-      mmaH(fh0, b0c, 0);
-      readH(fh0, pb, 1, 0);
-      mmaH(fh1, b0c, 1);
-      if constexpr (BA < 2) loadB(b0n, vb_s0, so_s0);
-      readH(fh1, pb, 1, 1);
-      mmaH(fh0, b1c, 0);
-      mmaH(fh1, b1c, 1);
-    }
-    transform(rn, pn);
-#ifndef U3_NO_SCHED
-    // Instruction order of the block (the scheduler's own choice bunches the transform behind the
-    // last MFMAs and issues every fragment read right in front of its MFMA): k-slab 0's fragment
-    // reads and the global loads first, a few transform instructions under their latency, then
-    // per MFMA two VALU instructions of the transform and at most one LDS read (k-slab 1's
-    // fragments, each as soon as the MFMAs that still read its registers have issued), one LDS
-    // write, one global load.
-#ifndef U3_VPM
-#define U3_VPM 2   // VALU instructions of the transform per MFMA
-#endif
-    if constexpr (ADB) {
-#pragma unroll
-      for (int k = 0; k < 2 * NP * MT * NT; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, U3_VPM, 0);
-      }
-    } else {
-      // four phases of 6 * HM * NT MFMAs (half 0 / half 1 of k-slab 0, then of k-slab 1).  Only
-      // the first half's fragments are read before the first MFMA (all eight waves read at once
-      // right after the barrier: every kilobyte in front of the first MFMA is exposed); the
-      // other reads trickle, one per MFMA, a phase ahead of their use.
-      // (Measured and dropped, profiles/r04_a_convbench_u3_loads_first.txt: pinning the chunk's raw-row
-      // and slab-1 B loads in front of the first MFMA with a VMEM-read group changes no layer by
-      // more than 2 %.)
-      __builtin_amdgcn_sched_group_barrier(0x100, NA * HM, 0);
-#pragma unroll
-      for (int ph = 0; ph < 4; ++ph) {
-#pragma unroll
-        for (int k = 0; k < NP * HM * NT; ++k) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, MATH == MATH_F16X3 ? 2 * U3_VPM : U3_VPM, 0);
-          if (ph < 3 && k < NA * HM) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-      }
-    }
-#endif
-    // ---- bookkeeping (branches from here on)
-#ifdef P3_DBG_TIME
-    const long long d_1 = clock64();
-    d_blk += d_1 - d_0;
-#endif
-    if constexpr (RB == 1) {
-      advance_raw();
-    } else if constexpr (load_pair) {
-      load_raw(rf);    // chunks g + 3, g + 4
-      advance_raw();
-      load_raw(rf2);
-      advance_raw();
-    }
-    ks3 += 6144;
-#ifdef P3_DBG_TIME
-    const long long d_2 = clock64();
-    d_book += d_2 - d_1;
-#endif
-    if (last_of_tile) {
-      // -------------------------------------------------------------- statistics
-      if (p.bn.acc != nullptr) {
-        wave_bn_tile<MT, NT>(acc, wbn, p.bn.acc, n0 + wave * NT * 32, p.N, p.M - m0, half, l31, PL::POST);
-        if (round == my_tiles - 1) wave_bn_flush(wbn, p.bn.acc, p.N, half, l31);  // in front of the stores
-      } else if (p.stat_partial != nullptr) {
-        const int col0 = n0 + wave * NT * 32;
-        if (p.stat_rows == 32 && MT > 1) {
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-            wave_stats_block<NT>(acc[i], p.stat_partial, m0 / 32 + i, p.M - (m0 + i * 32), col0, p.N,
-                                 half, l31, PL::POST);
-        } else if (p.stat_rows > 0 && p.stat_rows < BM)
-          wave_stats_fine<MT, NT>(acc, p.stat_partial, p.stat_rows, m0, p.M, col0, p.N, half, l31,
-                                  PL::POST);
-        else
-          wave_stats<MT, NT>(acc, p.stat_partial, m0 / BM, p.M - m0, BM, col0, p.N, half, l31, PL::POST);
-      }
-      // -------------------------------------------------------------- epilogue from registers
-      // (Measured alternatives, round 3, profiles/archive/r03_h_*: turning each 32x32 block around in a
-      // per-wave LDS square and storing 128-byte rows with 16-byte stores -- a quarter of the
-      // store instructions -- changes nothing (126 vs 122 us on the 64->256 layer): the burst
-      // drains at ~5.6 TB/s either way, and what is lost is that a wave's next loads queue
-      // behind its own stores in the one in-order vmcnt.  64-row tiles held to 128 VGPRs so that
-      // TWO workgroups share a CU and one computes while the other drains: 2x slower, 50
-      // registers spilled into the chunk loop.)
-      float e_sc[NT], e_sh[NT];
-      int e_voff[NT];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int col = n0 + (wave * NT + j) * 32 + l31;
-        const bool okc = col < p.N;
-        e_sc[j] = ((okc && p.scale) ? p.scale[col] : 1.f) * PL::POST;
-        e_sh[j] = (okc && p.shift) ? p.shift[col] : 0.f;
-        e_voff[j] = okc ? (int)((((long)(m0 + 4 * half)) * p.ldc + col) * 4) : BUF_OOB;
-      }
-      const int rows_left = p.M - (m0 + 4 * half);
-      wave_epilogue<MT, NT>(acc, e_sc, e_sh, e_voff, rows_left, p.ldc, p.act, p.residual != nullptr,
-                            rsrc_c, rsrc_r, true);
-      c = 0;
-      ks3 = 0;
-      if (++round < my_tiles) {
-        tile_of(round, m0, n0);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          vb[j] = vbn[j];
-          vbn[j] = BUF_OOB;
-        }
-        if (round + 1 < my_tiles) {
-          int m1, n1;
-          tile_of(round + 1, m1, n1);
-          vb_of(n1, vbn);
-        }
-      }
-    } else {
-      ++c;
-    }
-#ifdef P3_DBG_TIME
-    const long long d_3 = clock64();
-    d_epi += d_3 - d_2;
-#endif
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this thread's patch writes are in LDS
-    __builtin_amdgcn_s_barrier();
-#ifdef P3_DBG_TIME
-    d_bar += clock64() - d_3;
-#endif
-  };
-  auto& b0alt = [&]() -> auto& { if constexpr (BA == 2) return b0x; else return b0; }();
-  auto& b1alt = [&]() -> auto& { if constexpr (BA >= 1) return b1x; else return b1; }();
-  if constexpr (RB == 1) {
-    for (int g = 0; g < G; g += 2) {
-      // (B sets by chunk parity: BA = 0 uses b0 / b1 throughout; BA = 1 alternates b1 / b1x;
-      // BA = 2 alternates both)
-      chunk(g, ry, rx, rx, std::false_type{}, b0, b1, b0alt, b1alt);
-      if (g + 1 < G) chunk(g + 1, rx, ry, ry, std::false_type{}, b0alt, b1alt, b0, b1);
-    }
-  } else {
-    for (int g = 0; g < G; g += 4) {             // chunk g + 1 is transformed during chunk g
-      chunk(g, ry, rx, rx, std::false_type{}, b0, b1, b0alt, b1alt);
-      if (g + 1 < G) chunk(g + 1, rz, rx, ry, std::true_type{}, b0alt, b1alt, b0, b1);   // requests chunks g + 4, g + 5
-      if (g + 2 < G) chunk(g + 2, rw, rx, rx, std::false_type{}, b0, b1, b0alt, b1alt);
-      if (g + 3 < G) chunk(g + 3, rx, rz, rw, std::true_type{}, b0alt, b1alt, b0, b1);   // requests chunks g + 6, g + 7
-    }
-  }
-#ifdef P3_DBG_TIME
-  if (blockIdx.x == 8 && (tid == 0 || tid == (WAVES - 1) * 64)) {
-    const long long cy = clock64() - d_t0, w = wall_clock64() - d_w0;
-    printf("u3 wave %d: tiles %d chunks/tile %d: total %lld cycles = %lld ticks of 100 MHz (%.2f GHz): "
-           "MFMA+transform blocks %lld, bookkeeping %lld, epilogues %lld, barriers %lld\n",
-           wave, my_tiles, NC, cy, w, (double)cy / (double)w * 0.1, d_blk, d_book, d_epi, d_bar);
-  }
-#endif
-#endif
-}
-
-template <int BM, int DUAL, int WAVES, int LINEAR, int MATH>
-int launch_u3_(const IgemmParams& p, hipStream_t stream) {
-  constexpr int NV = DUAL == 2 ? 6 : 3;   // prologue vectors kept in LDS
-  const int smem_bytes = 2 * BM * Planes<MATH>::ROW + NV * p.Cin * 4;
-  constexpr int smem_max = 2 * BM * Planes<MATH>::ROW + NV * U3_MAX_CIN * 4;
-  auto kern = conv_u3_kernel<BM, DUAL, WAVES, LINEAR, MATH>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem_max);
-    if (e != hipSuccess) {
-      vlnce_set_error("conv_u3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_set = true;
-  }
-  IgemmParams q = p;
-  q.tiles_m = ceil_div(p.M, BM);
-  q.tiles_n = ceil_div(p.N, 256);
-  q.splitk = 1;
-  const long nwg = (long)q.tiles_m * q.tiles_n;
-  if (nwg <= 0 || nwg > 0x7fffffffL) {
-    vlnce_set_error("conv_u3: bad grid %ld", nwg);
-    return 1;
-  }
-  const int cus = x3_cus();
-  const unsigned grid = nwg <= cus ? (unsigned)nwg : (unsigned)cus;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), smem_bytes, stream, q);
-  VLNCE_CHECK_LAUNCH("conv_u3");
-  return 0;
-}
-
-// conv_s3_kernel: stride-1 1x1 convolutions with SHORT K (64 or 128 input channels) and wide N
-// (the 64->256 / 128->512 expansions of the bottlenecks: 268 / 134 MB of output per launch).
-// These launches are bound by the HBM write of their output, and in conv_u3_kernel they reach
-// 2.2-2.7 TB/s: a tile there is 2-4 K-chunks of MFMAs and a 128 KB store burst, and the loads of
-// the next tile (B fragments of its second k-slab, raw A two chunks ahead) queue behind the burst
-// in the wave's one in-order vmcnt, so a wave alternates between draining and computing
-// (profiles/archive/r03_h_u3_phase_timers_short_k.txt).  Here nothing a tile needs is loaded less than
-// a tile before its use, and a tile's stores are issued UNDER the next tile's MFMAs:
-//   * the B fragments of the wave's 32 columns for ALL of K stay in registers for the whole
-//     launch (K = 64: 48 VGPRs, K = 128: 96) -- a workgroup keeps its column tile;
-//   * the raw A rows of tile t + 2 (K = 128: t + 1) are requested while tile t is transformed
-//     (64-row tiles: one float4 per thread and chunk);
-//   * TWO accumulator sets: while the MFMAs of tile t fill one, the 32 stores of tile t - 1 drain
-//     the other, a few behind every k-slab (sched_group_barrier pins the interleave; the epilogue
-//     activation is a select so the slab body stays one basic block).  Stores are fire-and-forget:
-//     when the store queue is full the wave stalls at a store and the SIMD's other wave issues
-//     its MFMAs, so per tile a CU needs max(stores, MFMAs) instead of their sum.  Round 3's
-//     serial form (transform, barrier, MFMAs, then 32 stores at the CU's ~12 B/cycle = 54 % of
-//     the launch) measured 90.4 / 75.0 us on 64->256 / 128->512 at num_envs 64; this form 71.4 /
-//     72.1 us (profiles/r04_a_conv_s3_pipelined_epilogue.txt);
-//   * the first two tiles are peeled: the compiler's s_waitcnt at a loop header is the minimum
-//     over the paths into it, and entered from the preamble the wait for the raw rows would
-//     drain the previous tile's stores on every trip.
-// 8 waves (two per SIMD), wave w owns columns [32w, 32w + 32) of a 64 x 256 tile; one barrier
-// per tile.  Arithmetic, patch rows, fragment layout and statistics are conv_u3_kernel's.
-template <int NCC, int MATH>
-__global__ __launch_bounds__(512) void conv_s3_kernel(IgemmParams p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  typedef Planes<MATH> PL;
-  constexpr int P3_ROW = PL::ROW, NA = PL::NA, NP = PL::NP;
-  constexpr int BM = 64, MT = 2, KS = NCC * 2;
-  constexpr int CBUF = BM * P3_ROW;            // one chunk of a tile's patch
-  constexpr int PBUF = NCC * CBUF;             // one tile's patch
-  constexpr int SPS = 32 / KS;                 // stores of the previous tile behind each k-slab
-  extern __shared__ __attribute__((aligned(16))) char xsm[];  // [2][PBUF] + prologue vectors
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5;
-  const int l31 = lane & 31;
-  const int trow = tid >> 3;
-  const int lk4 = (tid & 7) * 4;
-
-  const int n0 = ((int)blockIdx.x % p.tiles_n) * 256;
-  const int wg = (int)blockIdx.x / p.tiles_n, nwg = (int)gridDim.x / p.tiles_n;
-  const int my_tiles = (p.tiles_m - wg + nwg - 1) / nwg;
-
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char*>(reinterpret_cast<const char*>(p.A)), 0, (int)p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char*>(reinterpret_cast<const char*>(p.Bfrag)), 0, (int)((long)p.N * p.K * 6),
-      0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<char*>(p.C), 0, (int)p.c_bytes, 0x00020000);
-  const float relu_floor = p.in_relu ? 0.f : -__builtin_huge_valf();
-  const bool relu_out = p.act == VLNCE_ACT_RELU;  // the launcher admits VLNCE_ACT_NONE / _RELU only
-
-  bf16x8 bres[KS][3];
-  {
-    const int vb = (n0 / 32 + wave) * KS * 3072 + lane * 16;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        bres[ks][q] = __builtin_bit_cast(
-            bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, vb + q * 1024, ks * 3072, 0));
-  }
-  // prologue vectors always in LDS here: the second accumulator set takes their registers
-  float* const vlds = reinterpret_cast<float*>(xsm + 2 * PBUF);  // [3][NCC * 32]
-  if (tid < 8) {
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f}, one4 = {1.f, 1.f, 1.f, 1.f};
-#pragma unroll
-    for (int c = 0; c < NCC; ++c) {
-      f32x4 s_ = one4, t_ = zero4, c_ = zero4;
-      if (p.in_scale != nullptr) {
-        s_ = ldg4(p.in_scale + c * 32 + lk4);
-        t_ = ldg4(p.in_shift + c * 32 + lk4);
-        if (p.in_center) c_ = ldg4(p.in_center + c * 32 + lk4);
-      }
-      *reinterpret_cast<f32x4*>(vlds + c * 32 + lk4) = s_;
-      *reinterpret_cast<f32x4*>(vlds + NCC * 32 + c * 32 + lk4) = t_;
-      *reinterpret_cast<f32x4*>(vlds + 2 * NCC * 32 + c * 32 + lk4) = c_;
-    }
-  }
-  __syncthreads();
-  const int col = n0 + wave * 32 + l31;
-  const float e_sc = (p.scale ? p.scale[col] : 1.f) * PL::POST;
-  const float e_sh = p.shift ? p.shift[col] : 0.f;
-
-  // raw A ring: two tiles ahead for K = 64; ONE for K = 128, where the second
-  // accumulator set leaves no registers for it (with the stores spread over the MFMA phase the
-  // request of tile t + 1 sits behind the stores of tile t - 2 only, a whole tile old)
-  constexpr int RING = NCC > 2 ? 1 : 2;
-  f32x4 raw[RING][NCC];
-  auto load_raw = [&](f32x4 (&r)[NCC], int round) {
-    const int m = (wg + round * nwg) * BM + trow;
-    const int vo = (round < my_tiles && m < p.M) ? (m * p.lda + lk4) * 4 : BUF_OOB;
-#pragma unroll
-    for (int c = 0; c < NCC; ++c)
-      r[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, vo, c * 128, 0));
-  };
-#pragma unroll
-  for (int k = 0; k < RING; ++k) load_raw(raw[k], k);
-  f32x16 acc[2][MT];  // [tile parity][row block]
-#pragma unroll
-  for (int b = 0; b < 2; ++b)
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[b][i][r] = 0.f;
-  const int a_off = l31 * P3_ROW + half * 16;
-
-  WaveBn<1> wbn;   // BatchNorm finished in this launch (p.bn): the wave's running column sums
-  wave_bn_reset(wbn);
-  // statistics of a finished tile (raw accumulators, 32-row blocks)
-  auto stats = [&](const f32x16 (&a)[MT], int m0) {
-    if (p.bn.acc != nullptr) {
-      wave_bn_tile<MT, 1>(reinterpret_cast<const f32x16(&)[MT][1]>(a), wbn, p.bn.acc, n0 + wave * 32,
-                          p.N, p.M - m0, half, l31, PL::POST);
-    } else if (p.stat_partial != nullptr) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-        wave_stats_block<1>(reinterpret_cast<const f32x16(&)[1]>(a[i]), p.stat_partial,
-                            m0 / 32 + i, p.M - (m0 + i * 32), n0 + wave * 32, p.N, half, l31, PL::POST);
-    }
-  };
-  // stores [first, first + count) of the 32 of a finished tile; the registers are cleared behind
-  auto stores = [&](f32x16 (&a)[MT], int m0, int first, int count) {
-    const int rows_left = p.M - (m0 + 4 * half);
-    const int e_voff = (int)((((long)(m0 + 4 * half)) * p.ldc + col) * 4);
-#pragma unroll
-    for (int k = first; k < first + count; ++k) {
-      const int i = k >> 4, r2 = k & 15;
-      const int rw = i * 32 + (r2 & 3) + 8 * (r2 >> 2);
-      const float lin = a[i][r2] * e_sc + e_sh;
-      const float v = relu_out ? (lin > 0.f ? lin : 0.f) : lin;  // (act is none or ReLU: selects, no branch)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc_c,
-                                            rw < rows_left ? e_voff : BUF_OOB, rw * p.ldc * 4, 0);
-      a[i][r2] = 0.f;
-    }
-  };
-
-  // one tile: cur = accumulator set of this tile, prv = the set of the tile before it (its
-  // statistics and stores are issued here, under this tile's MFMAs)
-  auto tile = [&](int round, f32x4 (&r)[NCC], f32x16 (&cur)[MT], f32x16 (&prv)[MT]) {
-    const int m0 = (wg + round * nwg) * BM;
-    const int m0_prev = (wg + (round - 1) * nwg) * BM;
-    const bool has_prev = round > 0;
-    char* const pb = xsm + (round & 1) * PBUF;
-    const bool row_ok = m0 + trow < p.M;
-#pragma unroll
-    for (int c = 0; c < NCC; ++c) {
-      f32x4 v = r[c];
-      const f32x4 s_ = *reinterpret_cast<const f32x4*>(vlds + c * 32 + lk4);
-      const f32x4 t_ = *reinterpret_cast<const f32x4*>(vlds + NCC * 32 + c * 32 + lk4);
-      const f32x4 c_ = *reinterpret_cast<const f32x4*>(vlds + 2 * NCC * 32 + c * 32 + lk4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = fmaxf(fmaf(v[e] - c_[e], s_[e], t_[e]), relu_floor);
-        v[e] = row_ok ? v[e] : 0.f;
-      }
-      p3_split_store<MATH>(v, pb + c * CBUF + trow * P3_ROW + lk4 * 2);
-    }
-    load_raw(r, round + RING);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (has_prev) stats(prv, m0_prev);
-#pragma unroll
-    for (int c = 0; c < NCC; ++c)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        bf16x8 f[MT][NA];
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int q = 0; q < NA; ++q)
-            f[i][q] = *reinterpret_cast<const bf16x8*>(pb + c * CBUF + a_off + i * 32 * P3_ROW +
-                                                       q * 64 + s2 * 32);
-#pragma unroll
-        for (int q = 0; q < NP; ++q)
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-            cur[i] = plane_mfma<MATH>(f[i][PL::PA[q]], bres[c * 2 + s2][PL::PB[q]], cur[i]);
-        // the previous tile's next SPS stores ride behind this slab's 12 MFMAs (a tile whose
-        // predecessor does not exist stores to the out-of-range offset: no branch in the body)
-        stores(prv, has_prev ? m0_prev : p.M, (c * 2 + s2) * SPS, SPS);
-        // schedule of the slab: its 12 MFMAs with the SPS stores spread evenly between them
-        // (K = 64: 2 MFMAs, store, 1 MFMA, store, four times; K = 128: 3 MFMAs, store, four times)
-        if constexpr (MATH == MATH_F16X3) {
-          // 6 MFMAs per slab: K = 64: MFMA, store, store, MFMA, store (x2, then 2 MFMAs + 2 stores);
-          // K = 128: 3 MFMAs, 2 stores, twice
-#pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            if constexpr (SPS == 8) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-            } else {
-              __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
-            }
-          }
-        } else {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            if constexpr (SPS == 8) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);  // VMEM write
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-            } else {
-              __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-            }
-          }
-        }
-      }
-  };
-  // The first two tiles are peeled: the compiler's s_waitcnt at a loop header is the minimum
-  // over the paths into it, and entered straight from the preamble the first wait for raw rows
-  // would be vmcnt(3) on EVERY trip -- i.e. the stores of the tile before would be drained every
-  // second tile (round 3's unpeeled form had exactly that: vmcnt(3) / vmcnt(35) alternated in its ISA).
-  // Behind the peeled tiles both ways into the loop have a tile's 32 stores after the request.
-  if (my_tiles <= 0) return;  // (cannot happen with launch_s3's grid; uniform per workgroup)
-  tile(0, raw[0], acc[0], acc[1]);
-  if (1 < my_tiles) tile(1, raw[RING - 1], acc[1], acc[0]);
-  for (int round = 2; round < my_tiles; round += 2) {
-    tile(round, raw[0], acc[0], acc[1]);
-    if (round + 1 < my_tiles) tile(round + 1, raw[RING - 1], acc[1], acc[0]);
-  }
-  // the last tile's epilogue has nothing left to hide under
-  {
-    const int m0 = (wg + (my_tiles - 1) * nwg) * BM;
-    if ((my_tiles - 1) & 1) {
-      stats(acc[1], m0);
-      if (p.bn.acc != nullptr) wave_bn_flush(wbn, p.bn.acc, p.N, half, l31);  // in front of the stores
-      stores(acc[1], m0, 0, 32);
-    } else {
-      stats(acc[0], m0);
-      if (p.bn.acc != nullptr) wave_bn_flush(wbn, p.bn.acc, p.N, half, l31);
-      stores(acc[0], m0, 0, 32);
-    }
-  }
-#endif
-}
-
-template <int NCC, int MATH>
-int launch_s3(const IgemmParams& p, hipStream_t stream) {
-  constexpr int smem_bytes = 2 * NCC * 64 * Planes<MATH>::ROW + 3 * NCC * 32 * 4;  // two tile patches + the prologue vectors
-  auto kern = conv_s3_kernel<NCC, MATH>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e != hipSuccess) {
-      vlnce_set_error("conv_s3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_set = true;
-  }
-  IgemmParams q = p;
-  q.tiles_m = ceil_div(p.M, 64);
-  q.tiles_n = p.N / 256;
-  q.splitk = 1;
-  const int cus = x3_cus();
-  long grid = (long)q.tiles_m * q.tiles_n;
-  if (grid > cus) grid = cus - cus % q.tiles_n;  // resident workgroups, a multiple of tiles_n
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem_bytes, stream, q);
-  VLNCE_CHECK_LAUNCH("conv_s3");
-  return 0;
-}
-
-template <int BM, int DUAL, int WAVES, int MATH>
-int launch_u3(const IgemmParams& p, hipStream_t stream) {
-  return p.stride == 1 ? launch_u3_<BM, DUAL, WAVES, 1, MATH>(p, stream)
-                       : launch_u3_<BM, DUAL, WAVES, 0, MATH>(p, stream);
 }
 
 // w_ohwi [N][KH][KW][Cin] fp32 -> B fragments [N/32][K/16][3][64 lanes][8 bf16]: k-slab
@@ -1740,7 +832,7 @@ int p3_try_launch_(const IgemmParams& p, hipStream_t stream) {
       (p.act == VLNCE_ACT_NONE || p.act == VLNCE_ACT_RELU) &&
       (s3_env == 2 || (long)ceil_div(p.M, 64) * (p.N / 256) >= 4L * x3_cus()))
   {
-    return p.Cin == 64 ? launch_s3<2, MATH>(p, stream) : launch_s3<4, MATH>(p, stream);
+    return s3_launch(p, stream);
   }
   const int u3_env = vlnce_opt(VLNCE_OPT_U3);
   const int u3_waves = vlnce_opt(VLNCE_OPT_U3_WAVES);
@@ -1758,14 +850,8 @@ int p3_try_launch_(const IgemmParams& p, hipStream_t stream) {
     if (u3_env == 1 && eff(128) < 0.8 && p.K >= 512 && eff(64) >= 0.8) bm = 64;
     if (eff(bm) >= 0.8 || u3_env >= 2) {
       const int kind = !dual ? 0 : (p.in2_scale != nullptr ? 2 : 1);
-      if (u3_waves == 4)   // one wave per SIMD, 64 x 256 tiles (a wave owns 64 x 64): experiment
-        return kind == 2 ? launch_u3<64, 2, 4, MATH>(p, stream)
-                         : kind ? launch_u3<64, 1, 4, MATH>(p, stream) : launch_u3<64, 0, 4, MATH>(p, stream);
-      if (bm == 128)
-        return kind == 2 ? launch_u3<128, 2, 8, MATH>(p, stream)
-                         : kind ? launch_u3<128, 1, 8, MATH>(p, stream) : launch_u3<128, 0, 8, MATH>(p, stream);
-      return kind == 2 ? launch_u3<64, 2, 8, MATH>(p, stream)
-                       : kind ? launch_u3<64, 1, 8, MATH>(p, stream) : launch_u3<64, 0, 8, MATH>(p, stream);
+      // (u3_waves == 4: one wave per SIMD, always 64 x 256 tiles -- conv_u3.hip)
+      return u3_launch(p, bm, kind, u3_waves == 4 ? 4 : 8, stream);
     }
   }
   if (mode_env == 2 && !dense) return -1;  // VLNCE_P3=2: only the patch (KxK) layers

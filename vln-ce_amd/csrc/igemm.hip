@@ -3,7 +3,8 @@
 //     the trainable tail, the 7x7 stems, the handful-of-tiles layers, VLNCE_CONV_MATH=f32;
 //   * conv_x3_kernel (further down): fp32 operands split into three bf16 planes, six plane
 //     products on v_mfma_f32_32x32x16_bf16 -- the 1x1 / strided convolutions of the frozen trunks
-//     that conv_p3.hip (conv_p3_kernel / conv_u3_kernel / conv_s3_kernel) does not take.
+//     that the router in conv_p3.hip (conv_p3_kernel / conv_u3_kernel / conv_s3_kernel, a file
+//     each) does not take.
 //
 //   C[M,N] = epilogue( A[M,K] * B[K,N] )
 //
@@ -571,11 +572,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmParams p) {
         for (int i = 0; i < MT; ++i)
 #pragma unroll
           for (int j = 0; j < NT; ++j)
-#ifdef IGEMM_DBG_NOMFMA
-            acc[i][j][0] += af[i][e] * bf[j][e];
-#else
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bf[j][e], acc[i][j], 0, 0, 0);
-#endif
     }
     if (more) store_ab(smem + ((t + 1) & 1) * STAGE);
     __syncthreads();
@@ -585,11 +582,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmParams p) {
   // one partial per WAVE sub-tile (WTM rows x WTN columns): {sum, M2 about the sub-tile mean},
   // index (tile_m * WM + wm).  No cross-wave reduction and no barrier here; the finalize
   // kernels merge the partials in fp64.
-#ifdef IGEMM_DBG_NOSTATS  // bisection builds: -DIGEMM_DBG_NOSTATS / _NOSTORE / _NOMFMA
-  if (false) {
-#else
   if (p.stat_partial != nullptr) {
-#endif
     if (p.stat_rows > 0 && p.stat_rows < WTM)
       wave_stats_fine<MT, NT>(acc, p.stat_partial, p.stat_rows, m0 + wm * WTM, p.M, n0 + wn * WTN,
                               p.N, half, l31);
@@ -599,9 +592,6 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmParams p) {
   }
 
   // ------------------------------------------------------------------ epilogue
-#ifdef IGEMM_DBG_NOSTORE
-  if (acc[0][0][0] != 123456.f) return;  // (keeps the accumulators alive)
-#endif
   if (p.splitk > 1) {
     // partial sums of this K range: plain atomic accumulation (C was zeroed by the host entry)
 #pragma unroll
@@ -966,10 +956,7 @@ __global__ __launch_bounds__((WM * WN + X3_PRODUCERS) * 64) void conv_x3_kernel(
 
     // K-tile g of the stream goes to stage g & 1 once the matrix waves are done with K-tile
     // g - 2; iteration g: issue the loads of K-tile g + NSET - 1, write K-tile g
-#ifdef X3_DBG_TIME
-    long long d_pl = 0, d_pw = 0, d_pm = 0, d_ps = 0;
-    const long long d_p0 = clock64();
-#endif
+    DBG_T(long long d_pl = 0, d_pw = 0, d_pm = 0, d_ps = 0; const long long d_p0 = clock64();)
     setup_tile(0);
     load_vec();
 #pragma unroll
@@ -979,34 +966,26 @@ __global__ __launch_bounds__((WM * WN + X3_PRODUCERS) * 64) void conv_x3_kernel(
       for (int j = 0; j < NSET; ++j) {
         const int g = g0 + j;
         if (g < G_total) {
-#ifdef X3_DBG_TIME
-          const long long d_0 = clock64();
-#endif
+          DBG_T(const long long d_0 = clock64();)
           const int seen = x3_peek(empty + (g & 1));
           load(st[(j + NSET - 1) % NSET], sb[(j + NSET - 1) % NSET], g + NSET - 1 < G_total);
-#ifdef X3_DBG_TIME
-          const long long d_1 = clock64();
-#endif
+          DBG_T(const long long d_1 = clock64();)
           x3_wait(empty + (g & 1), seen, X3_MATRIX * (g >> 1));  // K-tile g-2 has been read
-#ifdef X3_DBG_TIME
-          const long long d_2 = clock64();
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSET - 1) * (A_ROWS * (1 + DUAL) + 3)) : "memory");
-          const long long d_3 = clock64();
-#endif
+          DBG_T(const long long d_2 = clock64();
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSET - 1) * (A_ROWS * (1 + DUAL) + 3)) : "memory");
+                const long long d_3 = clock64();)
           stash(st[j], sb[j], xsm + (g & 1) * STAGE_BYTES);
           if (lane == 0) x3_signal(full + (g & 1));  // (in LDS order behind this wave's stage writes)
           s_ci += BK;
           if (s_ci >= p.Cin) s_ci = 0;
           if (g + 1 < G_total) load_vec();
-#ifdef X3_DBG_TIME
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          const long long d_4 = clock64();
-          d_pl += d_1 - d_0; d_pw += d_2 - d_1; d_pm += d_3 - d_2; d_ps += d_4 - d_3;
-#endif
+          DBG_T(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                const long long d_4 = clock64();
+                d_pl += d_1 - d_0; d_pw += d_2 - d_1; d_pm += d_3 - d_2; d_ps += d_4 - d_3;)
         }
       }
     }
-#ifdef X3_DBG_TIME
+#ifdef VLNCE_DBG_TIME
     if (blockIdx.x == 8 && (tid == X3_MATRIX * 64 || tid == X3_MATRIX * 64 + 448))
       printf("x3 producer wave %d: total %lld: issue loads %lld, wait for matrix waves %lld, wait for "
              "data %lld, transform+write %lld\n", wave, (long long)(clock64() - d_p0), d_pl, d_pw, d_pm, d_ps);
@@ -1049,10 +1028,7 @@ __global__ __launch_bounds__((WM * WN + X3_PRODUCERS) * 64) void conv_x3_kernel(
         const_cast<char*>(reinterpret_cast<const char*>(p.residual ? p.residual : p.C)), 0,
         (int)p.c_bytes, 0x00020000);   // (ldr == ldc: the output's extent)
 
-#ifdef X3_DBG_TIME
-    const long long d_c0 = clock64(), d_w0 = wall_clock64();
-    long long d_wait = 0;
-#endif
+    DBG_T(const long long d_c0 = clock64(), d_w0 = wall_clock64(); long long d_wait = 0;)
     Frag fa, fb;
     WaveBn<NT> wbn;   // BatchNorm finished in this launch (p.bn): the wave's running column sums
     wave_bn_reset(wbn);
@@ -1062,9 +1038,7 @@ __global__ __launch_bounds__((WM * WN + X3_PRODUCERS) * 64) void conv_x3_kernel(
     x3_wait(full, x3_peek(full), X3_PRODUCERS);  // K-tile 0 is written (stage 0's first)
     read(fa, 0, 0);
     int g = 0;
-#ifdef X3_DBG_TIME
-    const long long d_c1 = clock64();
-#endif
+    DBG_T(const long long d_c1 = clock64();)
     for (int round = 0; round < my_tiles; ++round) {
       int m0, n0;
       tile_of(round, m0, n0);
@@ -1095,13 +1069,9 @@ __global__ __launch_bounds__((WM * WN + X3_PRODUCERS) * 64) void conv_x3_kernel(
         mma(fa);
         __builtin_amdgcn_sched_barrier(0);
         if (g + 1 < G_total) {
-#ifdef X3_DBG_TIME
-          const long long d_a = clock64();
-#endif
+          DBG_T(const long long d_a = clock64();)
           x3_wait(full + ((g + 1) & 1), seen, X3_PRODUCERS * (((g + 1) >> 1) + 1));  // K-tile g+1 is written
-#ifdef X3_DBG_TIME
-          d_wait += clock64() - d_a;
-#endif
+          DBG_T(d_wait += clock64() - d_a;)
           read(fa, (g + 1) & 1, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1143,7 +1113,7 @@ __global__ __launch_bounds__((WM * WN + X3_PRODUCERS) * 64) void conv_x3_kernel(
                             rsrc_c, rsrc_r, false);
     }
     __builtin_amdgcn_s_setprio(0);
-#ifdef X3_DBG_TIME
+#ifdef VLNCE_DBG_TIME
     if (blockIdx.x == 8 && tid == 0) {
       const long long c = clock64() - d_c0, w = wall_clock64() - d_w0;
       printf("x3 tiles %d KT %d: first K-tile after %lld cycles; total %lld cycles = %lld ticks of 100 MHz "

@@ -1,4 +1,5 @@
-// Definitions shared by the convolution / GEMM translation units (igemm.hip, conv_p3.hip).
+// Definitions shared by the convolution / GEMM translation units (igemm.hip, conv_*.hip,
+// wgrad_x6.hip, ...).
 #pragma once
 #include "common.h"
 #include <stdlib.h>
@@ -13,7 +14,16 @@ enum { A_IM2COL_V4 = 0, A_IM2COL_S = 1, A_TRANS = 2, A_BUF = 3 };
 enum { B_NK_V4 = 0, B_NK_S = 1, B_KN = 2, B_BUF = 3, B_IM2COL = 4 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr int BUF_OOB = (int)0x80000000;  // voffset beyond any buffer: the load returns zeros
+
+// In-kernel phase timers (clock64 around the phases of a role, one printf at the end of the kernel):
+// DBG_T(statements) is there in -DVLNCE_DBG_TIME builds only.
+#ifdef VLNCE_DBG_TIME
+#define DBG_T(...) __VA_ARGS__
+#else
+#define DBG_T(...)
+#endif
 
 struct IgemmParams {
   const float* A;
@@ -374,6 +384,17 @@ __device__ __forceinline__ void split_pair(float v0, float v1, unsigned (&w)[Pla
     }
   }
 }
+// x (4 consecutive k of one patch row of conv_p3 / u3 / s3) -> the A planes' 8-byte words,
+// round-to-nearest split
+template <int MATH>
+__device__ __forceinline__ void p3_split_store(f32x4 x, char* row_ptr) {
+  constexpr int NA = Planes<MATH>::NA;
+  unsigned w0[NA], w1[NA];
+  split_pair<MATH>(x[0], x[1], w0);
+  split_pair<MATH>(x[2], x[3], w1);
+#pragma unroll
+  for (int q = 0; q < NA; ++q) *reinterpret_cast<u32x2*>(row_ptr + q * 64) = u32x2{w0[q], w1[q]};
+}
 // one weight -> its three B-plane values (16-bit words)
 template <int MATH>
 __device__ __forceinline__ void split_weight(float v, unsigned short (&o)[3]) {
@@ -439,9 +460,15 @@ static inline int x3_lds_max() {
 // launch hands over (vlnce_prologue.w_format -> IgemmParams::math: MATH_BF16X6 or MATH_F16X3).
 static inline int conv_math() { return vlnce_opt(VLNCE_OPT_CONV_MATH) != 0; }
 
-// conv_p3.hip: the patch-resident bf16-plane convolution.  Returns -1 when the problem is not
-// one it covers (the caller falls through to conv_x3_kernel / igemm_kernel), else a C-ABI status.
+// conv_p3.hip: the router of the patch-resident plane convolutions (conv_p3 / u3 / s3 kernels).
+// Returns -1 when the problem is not one they cover (the caller falls through to conv_x3_kernel /
+// igemm_kernel), else a C-ABI status.
 int p3_try_launch(const IgemmParams& p, hipStream_t stream);
+// The kernels the router hands eligible problems to (it has tested eligibility):
+// conv_u3.hip: bm = 64 / 128 tile rows, dual_kind = DUAL of conv_u3_kernel, waves = 8, or 4 (64-row tiles)
+constexpr int U3_MAX_CIN = 4096;   // conv_u3_kernel: input channels whose prologue vectors fit its LDS
+int u3_launch(const IgemmParams& p, int bm, int dual_kind, int waves, hipStream_t stream);
+int s3_launch(const IgemmParams& p, hipStream_t stream);   // conv_s3.hip: Cin = 64 or 128
 int m3_try_launch(const IgemmParams& p, hipStream_t stream);   // conv_m3.hip
 // wgrad_x6.hip: the weight gradient on the 16-bit pipe (three bf16 planes); -1 = not covered
 int wgrad_x6_try_launch(const float* x, const float* dy, float* dw, const vlnce_conv_desc* d,
