@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 143 = this header */
+int vlnce_version(void); /* major*100 + minor; 144 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -645,6 +645,31 @@ int vlnce_gru_rollout_bwd(const float* dout, const float* dh_final, const float*
                           const float* aux, const float* hp, const uint8_t* mask,
                           const float* w_hh_t, float* dgi, float* dgh, float* dh0,
                           void* workspace, int T, int N, int H, vlnce_stream_t stream);
+/* The same for an LSTM state encoder (ABI 144; STATE_ENCODER.rnn_type = LSTM), gate order i, f, g, o:
+ * the decomposition, the exchange and its tags are the GRU's.  The cell state is unit-local: the
+ * thread that finishes (unit, episode) keeps c_t (backward: dc) in a register for all T steps, so
+ * only h crosses workgroups forward and the 4H pre-activation gate gradients backward (dgi is also
+ * the recurrent gradient: an LSTM has no separate dgh).  Same arithmetic and the same saved tensors
+ * as T calls of vlnce_rnn_step_fwd / _bwd with lstm = 1:
+ *   fwd: gi [T,N,4H] (x W_ih^T + b_ih), h0, c0 [N,H], mask [T,N] -> hp [T,N,H] (mask_t * h_{t-1}),
+ *        out [T,N,H], gates [T,N,4H] (i, f, g, o activated), aux [T,N,H] (c_t; step t uses
+ *        mask_t * c_{t-1}, c_{-1} = c0);
+ *   bwd: dout [T,N,H], dh_final, dc_final [N,H] (each NULL = zeros), c0 as given to fwd,
+ *        w_hh_t = W_hh^T [H,4H] -> dgi [T,N,4H], dh0, dc0 [N,H] (the step-0 mask applied).
+ * workspace: vlnce_lstm_rollout_workspace_bytes(N, H) = 2 * N * 4H pairs of 8 bytes, owned by the
+ * caller for the duration of the launch and zeroed by the call.  _supported: N in 1..16, H in
+ * {64,128,256,512}, at least H/16 compute units, and the LDS one workgroup of this (N, H) instance
+ * needs (up to 152 KB: the backward at N > 8, H = 512) within the device's limit per workgroup;
+ * where it returns 0 the entry points return an error and launch nothing.  Residency as above. */
+int vlnce_lstm_rollout_supported(int N, int H);
+long vlnce_lstm_rollout_workspace_bytes(int N, int H);
+int vlnce_lstm_rollout_fwd(const float* gi, const float* h0, const float* c0, const uint8_t* mask,
+                           const float* w_hh, const float* b_hh, float* hp, float* out, float* gates,
+                           float* aux, void* workspace, int T, int N, int H, vlnce_stream_t stream);
+int vlnce_lstm_rollout_bwd(const float* dout, const float* dh_final, const float* dc_final,
+                           const float* gates, const float* aux, const float* hp, const float* c0,
+                           const uint8_t* mask, const float* w_hh_t, float* dgi, float* dh0,
+                           float* dc0, void* workspace, int T, int N, int H, vlnce_stream_t stream);
 
 /* out[b, :] = mask[b] ? a[b, :] : b[b, :]  (NULL operand = zeros): packed-sequence
  * semantics of the instruction RNN (steps past a sample's length keep the state

@@ -157,6 +157,10 @@ _SIGNATURES = {
     "vlnce_gru_rollout_workspace_bytes": (C.c_long, [_I, _I]),
     "vlnce_gru_rollout_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vlnce_gru_rollout_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "vlnce_lstm_rollout_supported": (_I, [_I, _I]),
+    "vlnce_lstm_rollout_workspace_bytes": (C.c_long, [_I, _I]),
+    "vlnce_lstm_rollout_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "vlnce_lstm_rollout_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vlnce_rnn_step_supported": (_I, [_I, _I, _I]),
     "vlnce_rnn_step_fwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "vlnce_rnn_step_bwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
@@ -235,7 +239,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 143  # include/vlnce_hip.h
+    ABI = 144  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -825,6 +829,25 @@ class HipLib:
             _ptr(dout), _ptr(dh_final), _ptr(gates), _ptr(aux), _ptr(hp), _ptr(mask),
             _ptr(w_hh_t), _ptr(dgi), _ptr(dgh), _ptr(dh0), _ptr(workspace), T, N, H, _stream()),
             "vlnce_gru_rollout_bwd")
+
+    def lstm_rollout_supported(self, N, H):
+        return bool(self.dll.vlnce_lstm_rollout_supported(N, H))
+
+    def lstm_rollout_workspace_bytes(self, N, H):
+        return int(self.dll.vlnce_lstm_rollout_workspace_bytes(N, H))
+
+    def lstm_rollout_fwd(self, gi, h0, c0, mask, w_hh, b_hh, hp, out, gates, aux, workspace,
+                         T, N, H):
+        self._check(self.dll.vlnce_lstm_rollout_fwd(
+            _ptr(gi), _ptr(h0), _ptr(c0), _ptr(mask), _ptr(w_hh), _ptr(b_hh), _ptr(hp), _ptr(out),
+            _ptr(gates), _ptr(aux), _ptr(workspace), T, N, H, _stream()), "vlnce_lstm_rollout_fwd")
+
+    def lstm_rollout_bwd(self, dout, dh_final, dc_final, gates, aux, hp, c0, mask, w_hh_t, dgi,
+                         dh0, dc0, workspace, T, N, H):
+        self._check(self.dll.vlnce_lstm_rollout_bwd(
+            _ptr(dout), _ptr(dh_final), _ptr(dc_final), _ptr(gates), _ptr(aux), _ptr(hp), _ptr(c0),
+            _ptr(mask), _ptr(w_hh_t), _ptr(dgi), _ptr(dh0), _ptr(dc0), _ptr(workspace), T, N, H,
+            _stream()), "vlnce_lstm_rollout_bwd")
 
     def rnn_step_supported(self, N, H, lstm):
         if os.environ.get("VLNCE_RNN_STEP_FUSED", "1") == "0":  # A/B switch (scripts/bench_data_path.py)

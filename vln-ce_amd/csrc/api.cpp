@@ -32,7 +32,8 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // option "conv_math" defaults to 2.
 // 143: vlnce_bn_bwd takes a workspace (vlnce_bn_bwd_workspace_floats): partial sums instead of atomics;
 // vlnce_conv2d_prepare_weights / vlnce_weight_job (all weight images of a trainable trunk in one launch).
-extern "C" int vlnce_version(void) { return 143; }
+// 144: vlnce_lstm_rollout_supported / _workspace_bytes / _fwd / _bwd (the LSTM state-encoder rollout in one launch per direction).
+extern "C" int vlnce_version(void) { return 144; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)

@@ -994,10 +994,10 @@ def lstm_cell(x_gates, h_prev, c_prev, w_hh, b_hh):
 _ROLLOUT_WS = {}
 
 
-def _rollout_workspace(dev, N, H):
-    """The exchange area of a persistent rollout launch: one per (device, stream) -- launches on
+def _rollout_workspace(dev, nbytes):
+    """The exchange area of a persistent rollout launch (`nbytes`: the library's
+    gru_ / lstm_rollout_workspace_bytes of the launch): one per (device, stream) -- launches on
     one stream are ordered, so they can share it; the library zeroes it per call."""
-    nbytes = L().gru_rollout_workspace_bytes(N, H)
     if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
         return torch.empty(nbytes, dtype=torch.uint8, device=dev)  # lives in the graph's own pool
     key = (str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
@@ -1012,9 +1012,10 @@ class MaskedRNNSeqFn(Function):
     RNNStateEncoder.seq_forward semantics: h (and c) are multiplied by the not-done mask of step
     t before step t).  A T-step rollout of N episodes -- the cached-feature DAgger batch
     (dagger_trainer.py:39-114) or a DD-PPO minibatch (rollout_storage.py:154-276) -- costs
-    ONE launch forward and ONE backward for a GRU over N <= 16 episodes (gru_rollout.hip: the
-    recurrent weights stay in the registers of H/16 resident workgroups, one device-scope
-    barrier per step); otherwise 1-3 launches per step forward (mask, h W_hh^T, gates) and 2-3
+    ONE launch forward and ONE backward for a GRU or an LSTM over N <= 16 episodes
+    (gru_rollout.hip: the recurrent weights stay in the registers of H/16 resident workgroups,
+    one device-scope exchange per step; an LSTM's cell state never leaves its thread's register)
+    where the library reports the shape supported on the device; otherwise 1-3 launches per step forward (mask, h W_hh^T, gates) and 2-3
     backward (gates', dgates W_hh, mask + skip add) instead of one autograd cell per step.  The
     recurrent weight / bias gradients are ONE GEMM / column sum over all T*N rows instead of T
     accumulated ones.
@@ -1038,11 +1039,20 @@ class MaskedRNNSeqFn(Function):
         gi3, m2 = gi.view(T, N, GH), mask.view(T, N)
         h, c = h0, (_f32c(c0) if lstm else None)
         b_hh = _f32c(b_hh)
-        ctx.rollout = (not lstm) and T > 1 and lib.gru_rollout_supported(N, H)
+        # (a library without the LSTM entry points, e.g. the CPU simulator, steps an LSTM)
+        supported = getattr(lib, "lstm_rollout_supported", None) if lstm else lib.gru_rollout_supported
+        ctx.rollout = T > 1 and supported is not None and bool(supported(N, H))
         if ctx.rollout:  # the whole recurrence in ONE launch (gru_rollout.hip)
-            lib.gru_rollout_fwd(gi3, h0, m2.contiguous(), w_hh, b_hh, hp, out, gates, aux,
-                                _rollout_workspace(dev, N, H), T, N, H)
             ctx.lstm, ctx.dims = lstm, (T, N, H, GH)
+            if lstm:
+                ws = _rollout_workspace(dev, lib.lstm_rollout_workspace_bytes(N, H))
+                lib.lstm_rollout_fwd(gi3, h0, c, m2.contiguous(), w_hh, b_hh, hp, out, gates, aux,
+                                     ws, T, N, H)
+                ctx.save_for_backward(hp, gates, aux, m2, w_hh, c)
+                return out.view(T * N, H), out[T - 1], aux[T - 1]
+            lib.gru_rollout_fwd(gi3, h0, m2.contiguous(), w_hh, b_hh, hp, out, gates, aux,
+                                _rollout_workspace(dev, lib.gru_rollout_workspace_bytes(N, H)),
+                                T, N, H)
             ctx.save_for_backward(hp, gates, aux, m2, w_hh, h0)
             return out.view(T * N, H), out[T - 1], out[T - 1]
         fused = lib.rnn_step_supported(N, H, lstm)
@@ -1073,6 +1083,21 @@ class MaskedRNNSeqFn(Function):
         T, N, H, GH = ctx.dims
         lstm = ctx.lstm
         dev = hp.device
+        if ctx.rollout and lstm:
+            dgi = torch.empty((T, N, GH), device=dev, dtype=torch.float32)  # = dgh for an LSTM
+            dh0 = torch.empty((N, H), device=dev, dtype=torch.float32)
+            dc0 = torch.empty((N, H), device=dev, dtype=torch.float32)
+            lib.lstm_rollout_bwd(None if dout is None else _f32c(dout),
+                                 None if dh_fin is None else _f32c(dh_fin),
+                                 None if dc_fin is None else _f32c(dc_fin), gates, aux, hp, c0,
+                                 m2.contiguous(), w_hh.t().contiguous(), dgi, dh0, dc0,
+                                 _rollout_workspace(dev, lib.lstm_rollout_workspace_bytes(N, H)),
+                                 T, N, H)
+            dw = torch.empty_like(w_hh)
+            lib.gemm(dgi.view(T * N, GH), GH, 1, hp.view(T * N, H), H, 1, dw, H, GH, H, T * N)
+            db = torch.empty((GH,), device=dev, dtype=torch.float32)
+            lib.colsum(dgi.view(T * N, GH), GH, T * N, GH, db, 0)
+            return None, dgi.view(T * N, GH), dh0, dc0, None, dw, db
         if ctx.rollout:
             dgi = torch.empty((T, N, GH), device=dev, dtype=torch.float32)
             dgh = torch.empty_like(dgi)
@@ -1082,7 +1107,8 @@ class MaskedRNNSeqFn(Function):
                 carry = _f32c(dc_fin) if carry is None else carry + dc_fin
             lib.gru_rollout_bwd(None if dout is None else _f32c(dout), carry, gates, aux, hp,
                                 m2.contiguous(), w_hh.t().contiguous(), dgi, dgh, dh0,
-                                _rollout_workspace(dev, N, H), T, N, H)
+                                _rollout_workspace(dev, lib.gru_rollout_workspace_bytes(N, H)),
+                                T, N, H)
             dw = torch.empty_like(w_hh)
             lib.gemm(dgh.view(T * N, GH), GH, 1, hp.view(T * N, H), H, 1, dw, H, GH, H, T * N)
             db = torch.empty((GH,), device=dev, dtype=torch.float32)
