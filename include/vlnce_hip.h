@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 144 = this header */
+int vlnce_version(void); /* major*100 + minor; 145 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -424,6 +424,12 @@ int vlnce_adaptive_avgpool(const float* x, float* y, int N, int H, int W, int C,
  * accumulate != 0 (ABI 143): dW += instead of dW = (the call does not zero dW). */
 int vlnce_conv2d_wgrad(const float* x, const float* dy, float* dw_ohwi, const vlnce_conv_desc* d,
                        const float* dy_pow2, int P, int accumulate, vlnce_stream_t stream);
+/* Which kernel the calling thread's last vlnce_conv2d_wgrad was dispatched to (ABI 145; -1 before the
+ * thread's first call).  No reference counterpart. */
+#define VLNCE_WGRAD_PATH_F32 0     /* igemm_kernel<A_TRANS, B_IM2COL>, v_mfma_f32_32x32x2_f32 */
+#define VLNCE_WGRAD_PATH_X6_BF16 1 /* wgrad_x6_kernel, three bf16 planes per operand          */
+#define VLNCE_WGRAD_PATH_X6_F16 2  /* wgrad_x6_kernel, fp16 planes (dy_pow2 given)            */
+int vlnce_conv2d_wgrad_last_path(void);
 /* BatchNorm2d backward through y = act(x*gamma*rstd + (beta - mean*gamma*rstd) (+ residual)):
  * g = dy*[y>0] when relu; dbeta = sum g; dgamma = sum g*xhat;
  * dx = gamma*rstd*(g - dbeta/M - xhat*dgamma/M) with batch statistics, gamma*rstd*g with
@@ -444,7 +450,10 @@ int vlnce_bn_bwd(const float* dy, const float* y, const float* x, const float* m
                  int use_batch_stats, float* dx, float* dres, float* dgamma, float* dbeta,
                  float* workspace, float* pow2, int P, vlnce_stream_t stream);
 /* GroupNorm backward (same conventions; mean/rstd are [N,groups]); workspace from
- * vlnce_gn_bwd_workspace_floats() floats; pow2 / P as vlnce_bn_bwd. */
+ * vlnce_gn_bwd_workspace_floats() floats ([N,chunks,C,2] partial sums, [N,groups,2] group sums padded to a
+ * multiple of 4 floats, [N,chunks,C,2] partial maxima, [N] bounds, [N,C,2] per-sample shares of dbeta /
+ * dgamma, which are added up in sample order: no atomics, the same bits on every call; chunks =
+ * ceil(HW / 128)); pow2 / P as vlnce_bn_bwd. */
 size_t vlnce_gn_bwd_workspace_floats(int Nimg, int HW, int C, int groups);
 int vlnce_gn_bwd(const float* dy, const float* y, const float* x, const float* mean,
                  const float* rstd, const float* gamma, int Nimg, int HW, int C, int groups,

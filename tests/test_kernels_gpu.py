@@ -786,42 +786,63 @@ def test_fused_bn_consumers(hip):
 
 
 # ------------------------------------------------------------------ trunk backward kernels
+# last field: the kernel the default launch must land on (vlnce_conv2d_wgrad_last_path): X6 = the plane
+# kernel wgrad_x6_kernel (Cin % 32 == 0, Cout % 32 == 0, M = N*Ho*Wo >= 256 pixels), F32 = the fp32-MFMA
+# igemm_kernel<A_TRANS, B_IM2COL>
+F32, X6 = 0, 1
 WGRAD_CASES = [
-    # name,        N,  H,  W, Cin, Cout, k, s, p
-    ("1x1",        2, 16, 16,  64, 128, 1, 1, 0),
-    ("3x3",        2, 16, 16,  64,  64, 3, 1, 1),
-    ("3x3s2",      3, 15, 17,  64, 128, 3, 2, 1),
-    ("1x1s2",      2, 16, 16, 128, 256, 1, 2, 0),
-    ("stem_rgb",   2, 64, 64,   3,  64, 7, 2, 3),
-    ("stem_depth", 2, 32, 32,   1,  32, 7, 2, 3),
-    ("ragged",     3,  7,  9,  36,  48, 3, 1, 1),
-    ("deep",       4,  8,  8, 512, 512, 3, 1, 1),
-    ("many_rows", 16, 32, 32,  64,  64, 3, 1, 1),     # split-K over 16384 pixels
+    # name,        N,  H,  W, Cin, Cout, k, s, p, path
+    ("1x1",        2, 16, 16,  64, 128, 1, 1, 0, X6),
+    ("3x3",        2, 16, 16,  64,  64, 3, 1, 1, X6),
+    ("3x3s2",      3, 15, 17,  64, 128, 3, 2, 1, F32),    # M = 216
+    ("1x1s2",      2, 16, 16, 128, 256, 1, 2, 0, F32),    # M = 128
+    ("stem_rgb",   2, 64, 64,   3,  64, 7, 2, 3, F32),
+    ("stem_depth", 2, 32, 32,   1,  32, 7, 2, 3, F32),
+    ("ragged",     3,  7,  9,  36,  48, 3, 1, 1, F32),
+    ("deep",       4,  8,  8, 512, 512, 3, 1, 1, X6),
+    ("many_rows", 16, 32, 32,  64,  64, 3, 1, 1, X6),     # split-K over 16384 pixels
     # round 6: wgrad_x6_kernel (three bf16 planes; Cin % 32 == 0, Cout % 32 == 0, >= 256 pixels)
-    ("depth_32",   3, 16, 16,  32,  32, 3, 1, 1),     # a 64-row tile half empty
-    ("wide_k",     2, 16, 16, 256,  64, 3, 1, 1),     # K = 2304: 18 column tiles
-    ("cout_160",   2, 16, 16,  64, 160, 1, 1, 0),     # 128-row tiles, the second one partial
-    ("ragged_m",   3, 13, 11,  64,  96, 3, 2, 1),     # 126 pixels... below the kernel's 256: fp32 kernel
-    ("ragged_m2",  5, 13, 11,  64,  96, 3, 1, 1),     # 715 pixels: last chunk partial
-    ("k_32",       2, 16, 16,  32, 128, 1, 1, 0),     # K = 32: a quarter of a column tile
+    ("depth_32",   3, 16, 16,  32,  32, 3, 1, 1, X6),     # a 64-row tile half empty
+    ("wide_k",     2, 16, 16, 256,  64, 3, 1, 1, X6),     # K = 2304: 18 column tiles
+    ("cout_160",   2, 16, 16,  64, 160, 1, 1, 0, X6),     # 128-row tiles, the second one partial
+    ("ragged_m",   3, 13, 11,  64,  96, 3, 2, 1, F32),    # 126 pixels... below the kernel's 256: fp32 kernel
+    ("ragged_m2",  5, 13, 11,  64,  96, 3, 1, 1, X6),     # 715 pixels: last chunk partial
+    ("k_32",       2, 16, 16,  32, 128, 1, 1, 0, X6),     # K = 32: a quarter of a column tile
+    # the plane kernel at stride 2 (hi = ho*stride - pad + r) ...
+    ("x6_3x3s2",     4, 16, 16,  64, 128, 3, 2, 1, X6),   # M = 256, TM = 128, K = 576: last column tile half
+    ("x6_3x3s2_odd", 5, 15, 17,  32,  64, 3, 2, 1, X6),   # M = 360, Ho*Wo = 72: chunks straddle images, TM = 64
+    ("x6_1x1s2",     4, 16, 16, 128, 256, 1, 2, 0, X6),   # M = 256
+    ("x6_1x1s2_odd", 3, 17, 19,  64,  96, 1, 2, 0, X6),   # M = 270: partial second 64-row tile and last chunk
+    # ... and with maps smaller than a 32-pixel chunk: several images per step of the pixel walk
+    ("x6_map4",     20,  4,  4,  64,  64, 3, 1, 1, X6),   # M = 320, Ho*Wo = 16: two images per chunk
+    ("x6_map3",     30,  3,  3,  32,  32, 3, 1, 1, X6),   # M = 270, Ho*Wo = 9: steps (3, 1, 2), every carry
+    ("x6_map2s2",   64,  4,  4,  64, 128, 3, 2, 1, X6),   # M = 256: stride 2 down to 2x2, 8 images per chunk
+    ("x6_map1",    256,  1,  1,  32,  32, 3, 1, 1, X6),   # M = 256: 1x1 map, only the centre tap in bounds
+    ("x6_ldx",       2, 16, 16,  64,  64, 3, 1, 1, X6, 96),   # M = 512: x rows 96 floats apart (ldx != Cin)
 ]
 
 
 @pytest.mark.parametrize("case", WGRAD_CASES, ids=[c[0] for c in WGRAD_CASES])
 def test_conv2d_wgrad(hip, case):
-    name, N, H, W, Cin, Cout, k, s, p = case
-    x = rnd(N, H, W, Cin, seed=1)
-    g = ops.conv_geometry(x, torch.empty(Cout, k, k, Cin), s, p)
+    name, N, H, W, Cin, Cout, k, s, p, path = case[:10]
+    ldx = case[10] if len(case) > 10 else Cin
+    # (ldx != Cin: the whole [N, H, W, ldx] tensor is the operand, the geometry names its first Cin channels)
+    x = rnd(N, H, W, ldx, seed=1)
+    g = ops.conv_geometry(x[..., :Cin], torch.empty(Cout, k, k, Cin), s, p, ldx=ldx)
+    assert (path == X6) == (Cin % 32 == 0 and Cout % 32 == 0 and N * g["Ho"] * g["Wo"] >= 256), name
     t = dict(x=x, dy=rnd(N, g["Ho"], g["Wo"], Cout, seed=2), dw=torch.zeros(Cout, k, k, Cin))
     cpu, gpu = both("conv2d_wgrad", t, dict(g=g))
+    assert hip.conv2d_wgrad_last_path() == path, name
     close(gpu["dw"], cpu["dw"], what="wgrad/" + name)
     # gradient-sized operands (1e-7: far below fp16's range -- the planes are bf16) and the fp32-MFMA
     # kernel behind option "wgrad_tile" = 1 agree with the same reference
     t2 = dict(t, dy=t["dy"] * 1e-7, dw=torch.zeros_like(t["dw"]))
     cpu2, gpu2 = both("conv2d_wgrad", t2, dict(g=g))
+    assert hip.conv2d_wgrad_last_path() == path, name
     close(gpu2["dw"], cpu2["dw"], what="wgrad/" + name + "/1e-7")
     with hip.options(wgrad_tile=1):
         cpu3, gpu3 = both("conv2d_wgrad", dict(t, dw=torch.zeros_like(t["dw"])), dict(g=g))
+        assert hip.conv2d_wgrad_last_path() == F32, name
     close(gpu3["dw"], cpu3["dw"], what="wgrad/" + name + "/fp32-MFMA")
     # accumulate: dW += (a trunk's backward zeroes one arena for all its layers)
     pre = rnd(Cout, k, k, Cin, seed=9)
@@ -835,18 +856,27 @@ def test_conv2d_wgrad(hip, case):
         pow2 = torch.stack([torch.full((8,), up), torch.full((8,), 1.0 / up)])
         t4 = dict(t, dy=dy, dw=torch.zeros_like(t["dw"]), dy_pow2=pow2)
         cpu4, gpu4 = both("conv2d_wgrad", t4, dict(g=g))
+        assert hip.conv2d_wgrad_last_path() == (2 if path == X6 else F32), (name, scale)
         close(gpu4["dw"], cpu4["dw"], what=f"wgrad/{name}/fp16 planes x{scale:g}")
         ref = cpu4["dw"].double()   # (close() carries an absolute 1e-6: relative, for the tiny dy)
         rel = float((gpu4["dw"].cpu().double() - ref).abs().max() / ref.abs().max())
         assert rel < 1e-4, (name, scale, rel)
 
 
-@pytest.mark.parametrize("stride,k,pad", [(1, 3, 1), (2, 3, 1), (2, 1, 0), (1, 1, 0), (2, 7, 3)])
-def test_conv_backward_matches_autograd(hip, stride, k, pad):
+CONV_BACKWARD_CASES = [(1, 3, 1), (2, 3, 1), (2, 1, 0), (1, 1, 0), (2, 7, 3)]
+
+
+@pytest.mark.parametrize("stride,k,pad,H,W",
+                         [c + (14, 18) for c in CONV_BACKWARD_CASES] + [c + (15, 17) for c in CONV_BACKWARD_CASES],
+                         ids=["%d-%d-%d" % c for c in CONV_BACKWARD_CASES]
+                         + ["%d-%d-%d-15x17" % c for c in CONV_BACKWARD_CASES])
+def test_conv_backward_matches_autograd(hip, stride, k, pad, H, W):
     """data + weight gradient of the host-side conv_backward (dgrad via the forward kernel
-    on flipped taps / zero-inserted dY) against torch autograd."""
+    on flipped taps / zero-inserted dY) against torch autograd.  The odd map leaves
+    (H + 2*pad - k) % stride != 0 for some of the stride-2 cases: input rows and columns past the
+    last window, which the zero-insertion and the [::stride] scatter must still cover."""
     from vlnce_amd.encoders import trunk_backward as tb
-    N, H, W, Cin, Cout = 2, 14, 18, 32, 64
+    N, Cin, Cout = 2, 32, 64
     x = rnd(N, H, W, Cin, seed=3)
     w = rnd(Cout, k, k, Cin, seed=4) * 0.2
     xr = x.permute(0, 3, 1, 2).clone().requires_grad_(True)

@@ -79,6 +79,7 @@ _SIGNATURES = {
     "vlnce_option_default": (_I, [C.c_char_p, C.POINTER(_I)]),
     "vlnce_conv2d_split_weights": (_I, [_P, _P, C.c_long, _I, _P]),
     "vlnce_conv2d_last_path": (_I, []),
+    "vlnce_conv2d_wgrad_last_path": (_I, []),
     "vlnce_embedding_bwd": (_I, [_P, _P, _P, _L, _I, _L, _L, _P]),
     "vlnce_conv2d_pack_bytes": (C.c_long, [C.POINTER(ConvDesc)]),
     "vlnce_conv2d_pack_weights": (_I, [_P, _P, C.POINTER(ConvDesc), _I, _P]),
@@ -239,7 +240,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 144  # include/vlnce_hip.h
+    ABI = 145  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -415,6 +416,9 @@ class HipLib:
 
     def conv2d_last_path(self):
         return int(self.dll.vlnce_conv2d_last_path())
+
+    def conv2d_wgrad_last_path(self):
+        return int(self.dll.vlnce_conv2d_wgrad_last_path())
 
     def conv2d_pack_bytes(self, g):
         d = self._desc(g)

@@ -33,7 +33,10 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // 143: vlnce_bn_bwd takes a workspace (vlnce_bn_bwd_workspace_floats): partial sums instead of atomics;
 // vlnce_conv2d_prepare_weights / vlnce_weight_job (all weight images of a trainable trunk in one launch).
 // 144: vlnce_lstm_rollout_supported / _workspace_bytes / _fwd / _bwd (the LSTM state-encoder rollout in one launch per direction).
-extern "C" int vlnce_version(void) { return 144; }
+// 145: vlnce_conv2d_wgrad_last_path (which weight-gradient kernel the thread's last vlnce_conv2d_wgrad ran on).
+// vlnce_gn_bwd_workspace_floats grows: the [N,groups,2] segment is padded to 16 bytes, and [N,C,2] per-sample
+// shares of dgamma / dbeta are added up in sample order (no atomics).
+extern "C" int vlnce_version(void) { return 145; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)

@@ -320,11 +320,13 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(
 }
 
 // one block per sample: s1[g] = sum_c gamma_c * SG[c], s2[g] = sum_c gamma_c * SGX[c];
-// dgamma[c] += SGX[c], dbeta[c] += SG[c]  (atomics across samples)
+// sums[n][c] = {SG[c], SGX[c]}: the sample's share of dbeta / dgamma, added up over the samples in a
+// fixed order by gn_bwd_param_grads_kernel (fp32 atomics across the samples' blocks gave dgamma and
+// dbeta a last bit that changed from call to call with three samples or more)
 __global__ __launch_bounds__(256) void gn_bwd_finalize_kernel(
     const float* __restrict__ partial, int C, int groups, int chunks,
     const float* __restrict__ gamma, float* __restrict__ s12 /* [N,groups,2] */,
-    float* __restrict__ dgamma, float* __restrict__ dbeta,
+    float* __restrict__ sums /* [N,C,2] */,
     const float* __restrict__ tops_partial, const float* __restrict__ rstd, float inv,
     float* __restrict__ bound /* [N] or null */) {
   extern __shared__ float sh[];  // [C][2]
@@ -339,8 +341,8 @@ __global__ __launch_bounds__(256) void gn_bwd_finalize_kernel(
     }
     sh[c * 2] = sg;
     sh[c * 2 + 1] = sgx;
-    atomicAdd(dbeta + c, sg);
-    atomicAdd(dgamma + c, sgx);
+    sums[((long)n * C + c) * 2] = sg;
+    sums[((long)n * C + c) * 2 + 1] = sgx;
   }
   __syncthreads();
   for (int g_ = threadIdx.x; g_ < groups; g_ += 256) {
@@ -374,6 +376,22 @@ __global__ __launch_bounds__(256) void gn_bwd_finalize_kernel(
   if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) bound[n] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+}
+
+// dbeta[c] = sum_n SG[n][c], dgamma[c] = sum_n SGX[n][c], samples in order
+__global__ __launch_bounds__(256) void gn_bwd_param_grads_kernel(const float* __restrict__ sums,
+                                                                 int Nimg, int C,
+                                                                 float* __restrict__ dgamma,
+                                                                 float* __restrict__ dbeta) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  float sg = 0.f, sgx = 0.f;
+  for (int n = 0; n < Nimg; ++n) {
+    sg += sums[((long)n * C + c) * 2];
+    sgx += sums[((long)n * C + c) * 2 + 1];
+  }
+  dbeta[c] = sg;
+  dgamma[c] = sgx;
 }
 
 // dx = rstd * (g*gamma - s1/cnt - xhat*s2/cnt)
@@ -669,6 +687,26 @@ inline BnBwdPlan bn_bwd_plan(long M, int C) {
   p.slices = ceil_div(M, p.rpb);
   return p;
 }
+
+// workspace of vlnce_gn_bwd, in floats from its base: partial [N,chunks,C,2] | s12 [N,groups,2], the
+// segment rounded up to a multiple of 4 floats | tops_partial [N,chunks,C,2] | bound [N] | sums [N,C,2].
+// gn_bwd_partial4_kernel writes partial and tops_partial 16 bytes at a time, so both must start on a
+// 16-byte boundary of a 16-byte aligned workspace: C % 4 == 0 there, and N*groups*2 is padded here.
+struct GnBwdLayout {
+  int chunks;
+  size_t s12, tops_partial, bound, sums, total;
+};
+inline GnBwdLayout gn_bwd_layout(int Nimg, int HW, int C, int groups) {
+  GnBwdLayout l;
+  l.chunks = ceil_div(HW, GN_CHUNK);
+  const size_t per_cc = (size_t)Nimg * l.chunks * C * 2;
+  l.s12 = per_cc;
+  l.tops_partial = l.s12 + (((size_t)Nimg * groups * 2 + 3) & ~(size_t)3);
+  l.bound = l.tops_partial + per_cc;
+  l.sums = l.bound + (size_t)Nimg;
+  l.total = l.sums + (size_t)Nimg * C * 2;
+  return l;
+}
 }  // namespace
 
 extern "C" size_t vlnce_bn_bwd_workspace_floats(long M, int C) {
@@ -734,7 +772,8 @@ extern "C" int vlnce_gn_bwd(const float* dy, const float* y, const float* x, con
                             const float* rstd, const float* gamma, int Nimg, int HW, int C,
                             int groups, int relu, float* dx, float* dres, float* dgamma,
                             float* dbeta,
-                            float* workspace /* [N,chunks,C,2] + [N,groups,2] + [N,chunks,C,2] + [N] */,
+                            float* workspace /* [N,chunks,C,2] + [N,groups,2] padded to a multiple of 4
+                                                floats + [N,chunks,C,2] + [N] + [N,C,2]: gn_bwd_layout */,
                             float* pow2, int P, vlnce_stream_t stream) {
   VLNCE_CHECK_ARG(dy && x && mean && rstd && dx && dgamma && dbeta && workspace,
                   "gn_bwd: null argument");
@@ -742,12 +781,13 @@ extern "C" int vlnce_gn_bwd(const float* dy, const float* y, const float* x, con
   VLNCE_CHECK_ARG(groups > 0 && C % groups == 0, "gn_bwd: C %% groups != 0");
   VLNCE_CHECK_ARG(!pow2 || P > 0, "gn_bwd: pow2 needs P > 0");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(zero2_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, s, dgamma, dbeta, C);
-  const int chunks = ceil_div(HW, GN_CHUNK);
+  const GnBwdLayout lay = gn_bwd_layout(Nimg, HW, C, groups);
+  const int chunks = lay.chunks;
   float* partial = workspace;
-  float* s12 = workspace + (size_t)Nimg * chunks * C * 2;
-  float* tops_partial = s12 + (size_t)Nimg * groups * 2;
-  float* bound = tops_partial + (size_t)Nimg * chunks * C * 2;
+  float* s12 = workspace + lay.s12;
+  float* tops_partial = workspace + lay.tops_partial;
+  float* bound = workspace + lay.bound;
+  float* sums = workspace + lay.sums;
   const bool quads = C % 4 == 0 && Nimg <= 65535 &&
                      aligned16({dy, y, x, dx, dres, workspace});
   const int qwl = quads ? strip_log2(C / 4) : 0, strips = quads ? ceil_div(C / 4, 1 << qwl) : 0;
@@ -765,8 +805,10 @@ extern "C" int vlnce_gn_bwd(const float* dy, const float* y, const float* x, con
                        rstd, HW, C, groups, chunks, relu, partial);
   }
   hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(Nimg), dim3(256), (size_t)C * 2 * sizeof(float),
-                     s, partial, C, groups, chunks, gamma, s12, dgamma, dbeta, tops_partial, rstd,
+                     s, partial, C, groups, chunks, gamma, s12, sums, tops_partial, rstd,
                      1.f / ((float)HW * (float)(C / groups)), pow2 ? bound : nullptr);
+  hipLaunchKernelGGL(gn_bwd_param_grads_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, s, sums, Nimg, C,
+                     dgamma, dbeta);
   const long total = (long)Nimg * HW * C;
   if (quads) {
     const int lanes = 256 >> qwl;
@@ -791,7 +833,7 @@ extern "C" int vlnce_gn_bwd(const float* dy, const float* y, const float* x, con
 }
 
 extern "C" size_t vlnce_gn_bwd_workspace_floats(int Nimg, int HW, int C, int groups) {
-  return (size_t)Nimg * ceil_div(HW, GN_CHUNK) * C * 4 + (size_t)Nimg * groups * 2 + (size_t)Nimg;
+  return gn_bwd_layout(Nimg, HW, C, groups).total;
 }
 
 extern "C" int vlnce_maxpool3x3s2_argmax(const float* x, float* y, uint8_t* argmax, int N, int H,

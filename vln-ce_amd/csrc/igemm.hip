@@ -1752,6 +1752,9 @@ extern "C" int vlnce_gemm(const float* A, int lda, int transA, const float* B, i
   return 0;
 }
 
+static thread_local int g_wgrad_last_path = -1;
+extern "C" int vlnce_conv2d_wgrad_last_path(void) { return g_wgrad_last_path; }
+
 // dW[Cout, KH, KW, Cin] = sum over output pixels of dY[m, co] * im2col(X)[m, (r,q,ci)]
 extern "C" int vlnce_conv2d_wgrad(const float* x, const float* dy, float* dw_ohwi,
                                   const vlnce_conv_desc* d, const float* dy_pow2, int P,
@@ -1786,8 +1789,11 @@ extern "C" int vlnce_conv2d_wgrad(const float* x, const float* dy, float* dw_ohw
   // option "wgrad_tile" = 1 keeps every layer on the fp32-MFMA kernel below (A/B)
   if (vlnce_opt(VLNCE_OPT_WGRAD_TILE) != 1)
     if (const int rc = wgrad_x6_try_launch(x, dy, dw_ohwi, d, dy_pow2, dy_pow2 ? dy_pow2 + P : nullptr,
-                                           accumulate, reinterpret_cast<hipStream_t>(stream)); rc >= 0)
+                                           accumulate, reinterpret_cast<hipStream_t>(stream)); rc >= 0) {
+      g_wgrad_last_path = dy_pow2 ? VLNCE_WGRAD_PATH_X6_F16 : VLNCE_WGRAD_PATH_X6_BF16;
       return rc;
+    }
+  g_wgrad_last_path = VLNCE_WGRAD_PATH_F32;
   // option "wgrad_tile" = 128: 128x128 tiles where both output dimensions allow.  Measured slower on
   // the trainable-encoder step (46.7 vs 45.0 ms, profiles/archive/r03_g_*): fewer workgroups per
   // split-K slice, and the transposed-operand LDS writes do not get cheaper.  Default 64.
