@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 145 = this header */
+int vlnce_version(void); /* major*100 + minor; 146 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -232,6 +232,49 @@ int vlnce_conv2d_prepare_weights(const vlnce_weight_job* jobs_dev, const long* f
 #define VLNCE_CONV_PATH_M3 3  /* conv_m3_kernel, bf16 planes, small launches: no LDS staging, 4-way k split */
 int vlnce_conv2d_last_path(void);
 
+/* Which kernel INSTANCE that launch went to (ABI 146): behind each family sit several template
+ * instances with their own product schedule, scaling and epilogue, and the tests name the one a case
+ * must land on.  Set by the host code that picks the instance; -1 before the thread's first launch.
+ *   bits  0..1  family, = vlnce_conv2d_last_path()
+ *   bits  2..3  plane format of the launch: 1 / 2 (vlnce_prologue.w_format), 0 for the fp32 kernel
+ *   bits  4..7  kernel within the family (VLNCE_CONV_KERNEL_*)
+ *   bits  8..15 A, 16..23 B, 24..30 C: what tells that kernel's instances apart
+ *     P3 / conv_p3:  A = tile 1..6 ({128,256} {64,256} {256,128} {128,128} {256,64} {128,64} rows x
+ *                    columns, option "p3_tile"'s numbering), B = VLNCE_CONV_P3_DENSE / _GATHER / _DUAL
+ *     P3 / conv_u3:  A = tile rows (64 / 128), B = kind (0 one input, 1 two inputs, 2 two inputs
+ *                    each with its own normalisation), C = waves (4 / 8)
+ *     P3 / conv_s3:  A = Cin (64 / 128)
+ *     M3:            A = NT (32-column blocks per wave), B = KSPLIT (waves sharing a reduction),
+ *                    C = RB (32-row blocks per workgroup)
+ *     X3:            A = tile 1..4 ({128,128} {64,128} {128,64} {64,64}, option "x3_tile"'s
+ *                    numbering), B = 1 with the two-input prologue
+ *     F32:           A = the split-K factor of VLNCE_CONV_KERNEL_F32_SPLITK, else 0 */
+#define VLNCE_CONV_KERNEL(family, format, kernel, a, b, c) \
+  ((family) | ((format) << 2) | ((kernel) << 4) | ((a) << 8) | ((b) << 16) | ((c) << 24))
+#define VLNCE_CONV_KERNEL_FAMILY(v) ((v) & 3)
+#define VLNCE_CONV_KERNEL_FORMAT(v) (((v) >> 2) & 3)
+#define VLNCE_CONV_KERNEL_KIND(v) (((v) >> 4) & 15)
+#define VLNCE_CONV_KERNEL_A(v) (((v) >> 8) & 255)
+#define VLNCE_CONV_KERNEL_B(v) (((v) >> 16) & 255)
+#define VLNCE_CONV_KERNEL_C(v) (((v) >> 24) & 127)
+/* family P3 */
+#define VLNCE_CONV_KERNEL_P3 0 /* conv_p3_kernel */
+#define VLNCE_CONV_KERNEL_U3 1 /* conv_u3_kernel */
+#define VLNCE_CONV_KERNEL_S3 2 /* conv_s3_kernel */
+#define VLNCE_CONV_P3_DENSE 0  /* KxK: the patch in LDS            */
+#define VLNCE_CONV_P3_GATHER 1 /* 1x1: rows gathered               */
+#define VLNCE_CONV_P3_DUAL 2   /* 1x1 with the two-input prologue  */
+/* family F32 (igemm_kernel) */
+#define VLNCE_CONV_KERNEL_F32_BUF 0    /* A_BUF / B_BUF tiles (buffer-descriptor loaders)          */
+#define VLNCE_CONV_KERNEL_F32_SPLITK 1 /* 64x64 A_BUF tiles, reduction split A ways, atomic adds    */
+#define VLNCE_CONV_KERNEL_F32_V4 2     /* A_IM2COL_V4 / B_NK_V4 tiles (Cin % 4 == 0)               */
+#define VLNCE_CONV_KERNEL_F32_S 3      /* A_IM2COL_S / B_NK_S tiles (scalar loaders)               */
+#define VLNCE_CONV_KERNEL_F32_STEM3 4  /* 7x7 stem, Cin 3                                          */
+#define VLNCE_CONV_KERNEL_F32_STEM1 5  /* 7x7 stem, Cin 1                                          */
+#define VLNCE_CONV_KERNEL_F32_DUAL 6   /* A_BUF tiles with the two-input prologue                  */
+/* families X3 and M3 have one kernel each: 0 */
+int vlnce_conv2d_last_kernel(void);
+
 int vlnce_conv2d_fwd(const float* x, const float* w_ohwi, float* y,
                      const vlnce_conv_desc* d, const vlnce_prologue* pro,
                      const vlnce_epilogue* epi, vlnce_stream_t stream);
@@ -430,6 +473,15 @@ int vlnce_conv2d_wgrad(const float* x, const float* dy, float* dw_ohwi, const vl
 #define VLNCE_WGRAD_PATH_X6_BF16 1 /* wgrad_x6_kernel, three bf16 planes per operand          */
 #define VLNCE_WGRAD_PATH_X6_F16 2  /* wgrad_x6_kernel, fp16 planes (dy_pow2 given)            */
 int vlnce_conv2d_wgrad_last_path(void);
+/* ... and which instance (ABI 146; -1 before the thread's first call):
+ *   bits 0..3  vlnce_conv2d_wgrad_last_path()
+ *   bits 4..11 row tile over Cout: TM of wgrad_x6_kernel (64 / 128), or the square tile of the fp32 kernel
+ *   bit  12    the reduction over the pixels was split over workgroups (atomic adds into dW) */
+#define VLNCE_WGRAD_KERNEL(path, tm, split) ((path) | ((tm) << 4) | ((split) ? 1 << 12 : 0))
+#define VLNCE_WGRAD_KERNEL_PATH(v) ((v) & 15)
+#define VLNCE_WGRAD_KERNEL_TM(v) (((v) >> 4) & 255)
+#define VLNCE_WGRAD_KERNEL_SPLIT(v) (((v) >> 12) & 1)
+int vlnce_conv2d_wgrad_last_kernel(void);
 /* BatchNorm2d backward through y = act(x*gamma*rstd + (beta - mean*gamma*rstd) (+ residual)):
  * g = dy*[y>0] when relu; dbeta = sum g; dgamma = sum g*xhat;
  * dx = gamma*rstd*(g - dbeta/M - xhat*dgamma/M) with batch statistics, gamma*rstd*g with

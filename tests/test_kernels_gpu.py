@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_dispatch
 import hostsim
 from vlnce_amd import _lib, ops
 
@@ -37,6 +38,9 @@ def close(a, b, tol=1e-4, what=""):
     assert err <= tol * scale + 1e-6, f"{what}: max|d|={err:.3e} scale={scale:.3e}"
 
 
+CONV_LAUNCHED = []   # the kernel instance (HipLib.conv2d_last_kernel()) of every conv2d_fwd that both() ran
+
+
 def both(method, tensors, scalars):
     """Run lib.<method>(**tensors, **scalars) on the simulator (CPU) and on the HIP
     library (GPU copies); return ({name: cpu tensor}, {name: gpu tensor})."""
@@ -47,6 +51,8 @@ def both(method, tensors, scalars):
         gpu["w_split"] = ops.split_weights(gpu["w"])
         gpu["w_frag"] = ops.pack_weights(gpu["w"])
     getattr(_lib.get_lib(), method)(**gpu, **scalars)
+    if method == "conv2d_fwd":
+        CONV_LAUNCHED.append(_lib.get_lib().conv2d_last_kernel())
     torch.cuda.synchronize()
     return cpu, gpu
 
@@ -1194,20 +1200,48 @@ def test_split_weights_fp16_planes(hip):
     _f16_planes_check(planes, w.view(-1))
 
 
-def _conv_cases_under(hip, cases, want_path=None, **opts):
+def full_device():
+    """the instance a launch lands on depends on the CU count; tests/conv_dispatch.py and the
+    expectations below are written for the whole 256-CU device"""
+    return torch.cuda.get_device_properties(0).multi_processor_count == conv_dispatch.CUS
+
+
+def _conv_cases_under(hip, cases, want_path=None, expect=None, min_expected=1, **opts):
     """every case of `cases` through test_conv2d_fwd with the dispatch options `opts` set
     (vlnce_set_option: in-process, restored afterwards); `want_path`: the kernel family at
-    least one of the cases must really have been given to (vlnce_conv2d_last_path)."""
+    least one of the cases must really have been given to (vlnce_conv2d_last_path).
+    Per case (on the whole 256-CU device): each of its launches -- the one with the case's prologue /
+    epilogue and, for a `stats` case, the bare one with statistics -- ran on the instance
+    tests/conv_dispatch.py derives from the dispatch rules, and on what `expect(launch)` demands:
+    (kernel, a[, b[, c]]) of HipLib.conv2d_last_kernel(), or None for a launch the forced kernel
+    does not cover.  `expect` must have demanded something of at least `min_expected` launches."""
     seen = set()
     opts.setdefault("m3", 0)   # (conv_m3_kernel would take every unit-test shape: they are all small)
+    wrong, demanded = [], 0
     with hip.options(**opts):
         for case in cases:
+            del CONV_LAUNCHED[:]
             try:
                 test_conv2d_fwd(hip, case)
             except AssertionError as e:
                 raise AssertionError(f"case {case[0]} under options {opts}: {e}") from e
             seen.add(hip.conv2d_last_path())
+            ran = [(conv_dispatch.Launch.of_case(case), CONV_LAUNCHED[0])]
+            if case[9].get("stats"):
+                ran.append((conv_dispatch.Launch.of_case(case, stats=True), hip.conv2d_last_kernel()))
+            for launch, got in ran:
+                model = conv_dispatch.expected(launch, **opts)
+                if got != model:
+                    wrong.append((case[0], launch.stats, "got", got, "dispatch rules give", model))
+                want = expect(launch) if expect else None
+                if want is not None:
+                    demanded += 1
+                    if (got.kernel, got.a, got.b, got.c)[:len(want)] != tuple(want):
+                        wrong.append((case[0], launch.stats, "got", got, "forced", want))
     assert want_path is None or want_path in seen, (opts, seen)
+    if full_device():
+        assert not wrong, (opts, wrong)
+        assert expect is None or demanded >= min_expected, (opts, demanded)
 
 
 @pytest.mark.parametrize("tile", [1, 2, 3, 4])
@@ -1215,7 +1249,12 @@ def test_conv_x3_every_tile_shape(hip, tile):
     """conv_x3_kernel has four tile shapes chosen by problem size; force each one (option
     "x3_tile") over the conv cases, including several tiles per workgroup, ragged M, N below the
     tile width, the dual-input prologue and statistics partials."""
-    _conv_cases_under(hip, CONV_CASES, want_path=1, x3_tile=tile)
+    def expect(L):   # what neither conv_p3 (default: the stride-1 KxK layers it can tile) nor split-K takes
+        if (not conv_dispatch.reaches_plane_kernels(L)
+                or conv_dispatch.expected(L, m3=0, x3_tile=tile).family == "p3"):
+            return None
+        return ("conv_x3", tile, 1 if L.dual else 0)
+    _conv_cases_under(hip, CONV_CASES, want_path=1, expect=expect, min_expected=6, x3_tile=tile)
 
 
 # ------------------------------------------------------------------ patch-resident bf16-plane kernel
@@ -1288,6 +1327,7 @@ P3_CASES = [
     ("s3_rag_m",     1,  8, 20, 128, 256, 1, 1, 0, dict(stats=True)),             # 64 + 64 + 32 rows
     ("s3_many",     48, 32, 32,  64, 256, 1, 1, 0, dict(prologue=True, in_relu=True, center=True)),  # 3 tiles per workgroup
     ("s3_many_512", 40, 32, 32, 128, 512, 1, 1, 0, dict(stats=True)),             # two column tiles, 5 rounds
+    ("m3_1x1_n96",   2,  8,  8,  64,  96, 1, 1, 0, dict(scale=True, relu=True)),  # conv_m3<1,1,4>: K < 128, N % 64 != 0
 ]
 
 
@@ -1303,8 +1343,20 @@ def test_conv_m3_every_eligible_case(hip):
     3x3 / 5x5 / 1x1, strides 1 and 2, padding 0..2, ragged M, tiles across image borders, prologue
     with centre and ReLU, epilogue scale / shift / ReLU / residual, statistics partials of 32 and
     16 rows, N = 32 (one column block) to 768."""
-    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=3, m3=2)
-    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=3, m3=3)   # two row blocks per workgroup
+    def eligible(L):
+        return (L.Cin % 32 == 0 and L.Cout % 32 == 0 and not L.dual and L.Cin <= 2048
+                and not (L.residual and L.stats))
+
+    def expect2(L):
+        return ("conv_m3",) if eligible(L) else None
+
+    def expect3(L):   # the split-reduction wide cases: two row blocks per workgroup
+        if not eligible(L):
+            return None
+        split = L.K >= 128 and -(-L.M // 128) * (L.Cout // 64) < conv_dispatch.CUS
+        return ("conv_m3", 2, 4, 2) if L.Cout % 64 == 0 and split else ("conv_m3",)
+    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=3, expect=expect2, min_expected=40, m3=2)
+    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=3, expect=expect3, min_expected=40, m3=3)
 
 
 @pytest.mark.parametrize("tile", [1, 2, 3, 4, 5, 6])
@@ -1312,7 +1364,20 @@ def test_conv_p3_every_tile_shape(hip, tile):
     """conv_p3_kernel has six tile shapes chosen by problem size; force each one (option
     "p3_tile") over the conv cases: several tiles per workgroup, ragged M, N below the tile width,
     patches across image borders, the dual-input prologue, statistics."""
-    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=2, p3_tile=tile)
+    def expect(L, **o):   # every launch conv_p3 covers, that split-K does not take first, whose tile fits
+        if not conv_dispatch.p3_eligible(L) or (L.k == 1 and not o):
+            return None       # (option "p3" = 2, the default: the 1x1 layers are not conv_p3's)
+        if not conv_dispatch.reaches_plane_kernels(L):
+            return None
+        if not conv_dispatch.p3_tile_fits(L, hip.plane_format(), tile):
+            return None
+        return ("conv_p3", tile, "dual" if L.dual else "gather" if L.k == 1 else "dense")
+    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=2, expect=expect, min_expected=4, p3_tile=tile)
+    # ... and its 1x1 forms (rows gathered; the two-input prologue), which the default leaves to
+    # conv_u3 / conv_s3 / conv_x3: option "p3" = 1 with those two off
+    one = [c for c in CONV_CASES + P3_CASES if c[6] == 1]
+    _conv_cases_under(hip, one, want_path=2, expect=lambda L: expect(L, p3=1), min_expected=20,
+                      p3_tile=tile, p3=1, u3=0, s3=0)
 
 
 @pytest.mark.parametrize("mode", [2, 3])
@@ -1320,7 +1385,14 @@ def test_conv_u3_forced(hip, mode):
     """conv_u3_kernel (1x1, no producer waves) takes a layer only when its tiles fill the CUs,
     which no unit-test shape does: force it (option "u3" = 2: 64-row tiles, 3: 128-row tiles)
     over the 1x1 cases with N >= 256 -- prologue, statistics, stride 2, dual input, ragged M."""
-    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=2, u3=mode)
+    def expect(L):   # every 1x1 launch with N >= 256 -- but for what conv_s3's default rule takes first
+        if not (conv_dispatch.p3_eligible(L) and L.k == 1 and L.pad == 0 and L.Cout >= 256
+                and L.Cin <= conv_dispatch.U3_MAX_CIN and conv_dispatch.reaches_plane_kernels(L)):
+            return None
+        if conv_dispatch.expected(L, m3=0, u3=0).kernel == "conv_s3":
+            return None   # (s3_many_512: 1280 tiles of 64 rows, four per CU)
+        return ("conv_u3", 64 if mode == 2 else 128, {None: 0, "identity": 1, "bn": 2}[L.dual], 8)
+    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=2, expect=expect, min_expected=12, u3=mode)
 
 
 def test_conv_s3_forced(hip):
@@ -1329,7 +1401,10 @@ def test_conv_s3_forced(hip):
     gets at least four of its 64-row tiles; option "s3" = 2 sends every eligible shape to it:
     prologue + centre, statistics, epilogue scale / act, ragged M, one to five tiles per
     workgroup (the peeled first two and the loop), two column tiles."""
-    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=2, s3=2)
+    def expect(L):
+        ok = conv_dispatch.s3_eligible(L) and conv_dispatch.reaches_plane_kernels(L)
+        return ("conv_s3", L.Cin) if ok else None
+    _conv_cases_under(hip, CONV_CASES + P3_CASES, want_path=2, expect=expect, min_expected=10, s3=2)
 
 
 FORCED = [dict(), dict(m3=2), dict(u3=2), dict(u3=3), dict(s3=2), dict(p3_tile=1), dict(p3_tile=2),
@@ -1445,11 +1520,18 @@ def test_conv_p3_matches_fp64_better_than_1e_6(hip, fmt):
     """Both plane formats keep the convolution fp32-class: relative rms error against an fp64
     convolution of the same operands below 1e-6 (torch's own fp32 conv: ~2e-7), post-ReLU-like
     (non-negative) and signed activations."""
+    # (by default this launch is conv_m3_kernel's, and without it split-K's: 64 tiles of 64 x 64; the
+    # options below hand it to conv_p3_kernel, 128 x 128 tiles.  Every other instance:
+    # tests/test_conv_routes_gpu.py)
     for sign in (False, True):
         x = rnd(4, 16, 16, 256, seed=21)
         x = (x if sign else x.abs()).to(DEV)
         w = (rnd(256, 3, 3, 256, seed=22) * (256 * 9) ** -0.5).to(DEV)
-        y = ops.conv2d_nhwc(x, w, 1, 1, w_format=fmt)
+        with hip.options(m3=0, igemm_no_splitk=1, p3_tile=4):
+            y = ops.conv2d_nhwc(x, w, 1, 1, w_format=fmt)
+            ran = hip.conv2d_last_kernel()
+        assert (ran.family, ran.kernel, ran.fmt, ran.b) == ("p3", "conv_p3", fmt, "dense"), ran
+        assert ran.a == 4 or not full_device(), ran
         ref = F.conv2d(x.double().permute(0, 3, 1, 2), w.double().permute(0, 3, 1, 2), padding=1)
         ref = ref.permute(0, 2, 3, 1)
         rms = ((y.double() - ref).pow(2).mean() / ref.pow(2).mean()).sqrt().item()

@@ -7,6 +7,7 @@ or a tensor is not on a GPU the call raises.  (tests/hostsim.py swaps in a
 tensor-level simulator of this class to exercise the *host* logic on CPU; it
 lives under tests/ and is never importable from the product.)
 """
+import collections
 import ctypes as C
 import os
 import threading
@@ -33,6 +34,37 @@ def _buffer_format(explicit, *bufs):
     if len(tags) > 1:
         raise RuntimeError(f"weight buffers / w_format disagree on the plane format: {sorted(tags)}")
     return tags.pop() if tags else 1
+
+
+# ---- vlnce_conv2d_last_kernel / vlnce_conv2d_wgrad_last_kernel (VLNCE_CONV_KERNEL_* of the header), as names
+ConvKernel = collections.namedtuple("ConvKernel", "family kernel fmt a b c")
+ConvKernel.__doc__ = """family: "f32" | "x3" | "p3" | "m3" (= conv2d_last_path()); kernel: the kernel within it
+("conv_p3" | "conv_u3" | "conv_s3", "conv_m3", "conv_x3", "buf" | "splitk" | "v4" | "s" | "stem3" |
+"stem1" | "dual" of igemm_kernel); fmt: plane format 1 / 2 (0: fp32); a, b, c per kernel:
+  conv_p3: tile 1..6, mode "dense" | "gather" | "dual", 0      conv_u3: rows, kind 0..2, waves
+  conv_s3: Cin, 0, 0      conv_m3: NT, KSPLIT, RB      conv_x3: tile 1..4, dual 0 / 1, 0
+  splitk: the split factor, 0, 0"""
+WgradKernel = collections.namedtuple("WgradKernel", "path tm split")   # path = conv2d_wgrad_last_path()
+
+_FAMILIES = ("f32", "x3", "p3", "m3")
+_KERNELS = {"f32": ("buf", "splitk", "v4", "s", "stem3", "stem1", "dual"), "x3": ("conv_x3",),
+            "p3": ("conv_p3", "conv_u3", "conv_s3"), "m3": ("conv_m3",)}
+_P3_MODES = ("dense", "gather", "dual")
+
+
+def decode_conv_kernel(v):
+    if v < 0:
+        return None
+    family = _FAMILIES[v & 3]
+    kernel = _KERNELS[family][(v >> 4) & 15]
+    a, b, c = (v >> 8) & 255, (v >> 16) & 255, (v >> 24) & 127
+    if kernel == "conv_p3":
+        b = _P3_MODES[b]
+    return ConvKernel(family, kernel, (v >> 2) & 3, a, b, c)
+
+
+def decode_wgrad_kernel(v):
+    return None if v < 0 else WgradKernel(v & 15, (v >> 4) & 255, bool((v >> 12) & 1))
 
 
 class ConvDesc(C.Structure):
@@ -80,6 +112,8 @@ _SIGNATURES = {
     "vlnce_conv2d_split_weights": (_I, [_P, _P, C.c_long, _I, _P]),
     "vlnce_conv2d_last_path": (_I, []),
     "vlnce_conv2d_wgrad_last_path": (_I, []),
+    "vlnce_conv2d_last_kernel": (_I, []),
+    "vlnce_conv2d_wgrad_last_kernel": (_I, []),
     "vlnce_embedding_bwd": (_I, [_P, _P, _P, _L, _I, _L, _L, _P]),
     "vlnce_conv2d_pack_bytes": (C.c_long, [C.POINTER(ConvDesc)]),
     "vlnce_conv2d_pack_weights": (_I, [_P, _P, C.POINTER(ConvDesc), _I, _P]),
@@ -240,7 +274,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 145  # include/vlnce_hip.h
+    ABI = 146  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -419,6 +453,14 @@ class HipLib:
 
     def conv2d_wgrad_last_path(self):
         return int(self.dll.vlnce_conv2d_wgrad_last_path())
+
+    def conv2d_last_kernel(self):
+        """the kernel instance the calling thread's last conv2d_fwd ran on, decoded (ConvKernel)"""
+        return decode_conv_kernel(int(self.dll.vlnce_conv2d_last_kernel()))
+
+    def conv2d_wgrad_last_kernel(self):
+        """... and the last conv2d_wgrad's (WgradKernel)"""
+        return decode_wgrad_kernel(int(self.dll.vlnce_conv2d_wgrad_last_kernel()))
 
     def conv2d_pack_bytes(self, g):
         d = self._desc(g)

@@ -36,7 +36,9 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // 145: vlnce_conv2d_wgrad_last_path (which weight-gradient kernel the thread's last vlnce_conv2d_wgrad ran on).
 // vlnce_gn_bwd_workspace_floats grows: the [N,groups,2] segment is padded to 16 bytes, and [N,C,2] per-sample
 // shares of dgamma / dbeta are added up in sample order (no atomics).
-extern "C" int vlnce_version(void) { return 145; }
+// 146: vlnce_conv2d_last_kernel / vlnce_conv2d_wgrad_last_kernel (which kernel INSTANCE the thread's last
+// launch ran on: family, plane format, tile / mode / template arguments; VLNCE_CONV_KERNEL_*).
+extern "C" int vlnce_version(void) { return 146; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)

@@ -296,6 +296,7 @@ int launch_m3_(const IgemmParams& p, hipStream_t stream) {
 }
 template <int NT, int KSPLIT, int RB>
 int launch_m3(const IgemmParams& p, hipStream_t stream) {
+  note_conv_kernel(VLNCE_CONV_KERNEL(VLNCE_CONV_PATH_M3, p.math, 0, NT, KSPLIT, RB));
   return p.math == MATH_F16X3 ? launch_m3_<NT, KSPLIT, RB, MATH_F16X3>(p, stream)
                               : launch_m3_<NT, KSPLIT, RB, MATH_BF16X6>(p, stream);
 }

@@ -788,6 +788,9 @@ int p3_rows_for(const IgemmParams& p, int bm, bool dense) {
 // 128 rows the texture path carries 16 B/clk per CU, with 32 rows it would saturate (64 B/clk).
 template <int DUAL, int MODE, int MATH>
 int dispatch_p3(const IgemmParams& p, int tile, int rows, hipStream_t s) {
+  note_conv_kernel(VLNCE_CONV_KERNEL(VLNCE_CONV_PATH_P3, MATH, VLNCE_CONV_KERNEL_P3, tile + 1,
+                                     DUAL ? VLNCE_CONV_P3_DUAL : MODE == P3_DENSE ? VLNCE_CONV_P3_DENSE
+                                                                                  : VLNCE_CONV_P3_GATHER, 0));
   switch (tile) {
     case 0: return launch_p3<128, 256, 1, 8, DUAL, MODE, MATH>(p, rows, s);
     case 1: return launch_p3<64, 256, 1, 8, DUAL, MODE, MATH>(p, rows, s);

@@ -285,6 +285,7 @@ int launch_s3(const IgemmParams& p, hipStream_t stream) {
 }  // namespace
 
 int s3_launch(const IgemmParams& p, hipStream_t stream) {   // Cin is 64 or 128 (the router's test)
+  note_conv_kernel(VLNCE_CONV_KERNEL(VLNCE_CONV_PATH_P3, p.math, VLNCE_CONV_KERNEL_S3, p.Cin == 64 ? 64 : 128, 0, 0));
   if (p.math == MATH_F16X3)
     return p.Cin == 64 ? launch_s3<2, MATH_F16X3>(p, stream) : launch_s3<4, MATH_F16X3>(p, stream);
   return p.Cin == 64 ? launch_s3<2, MATH_BF16X6>(p, stream) : launch_s3<4, MATH_BF16X6>(p, stream);

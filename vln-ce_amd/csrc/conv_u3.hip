@@ -515,6 +515,9 @@ int launch_u3(const IgemmParams& p, hipStream_t stream) {
 
 template <int MATH>
 int u3_launch_(const IgemmParams& p, int bm, int dual_kind, int waves, hipStream_t stream) {
+  note_conv_kernel(VLNCE_CONV_KERNEL(VLNCE_CONV_PATH_P3, MATH, VLNCE_CONV_KERNEL_U3,
+                                     waves == 4 || bm != 128 ? 64 : 128, dual_kind == 2 ? 2 : dual_kind ? 1 : 0,
+                                     waves == 4 ? 4 : 8));
   if (waves == 4)   // one wave per SIMD, 64 x 256 tiles (a wave owns 64 x 64): experiment
     return dual_kind == 2 ? launch_u3<64, 2, 4, MATH>(p, stream)
                           : dual_kind ? launch_u3<64, 1, 4, MATH>(p, stream) : launch_u3<64, 0, 4, MATH>(p, stream);

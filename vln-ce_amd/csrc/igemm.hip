@@ -1357,6 +1357,8 @@ bool x3_plan(const IgemmParams& p, X3Plan* out) {
 }
 template <int DUAL, int MATH>
 int dispatch_x3_(const IgemmParams& p, const X3Plan& t, hipStream_t s) {
+  const int tile = t.bm == 128 ? (t.bn == 128 ? 1 : 3) : (t.bn == 128 ? 2 : 4);
+  note_conv_kernel(VLNCE_CONV_KERNEL(VLNCE_CONV_PATH_X3, MATH, 0, tile, DUAL, 0));
   if (t.bm == 128 && t.bn == 128) return launch_x3<128, 128, 2, 4, DUAL, MATH>(p, s);
   if (t.bm == 64 && t.bn == 128) return launch_x3<64, 128, 2, 4, DUAL, MATH>(p, s);
   if (t.bm == 128 && t.bn == 64) return launch_x3<128, 64, 4, 2, DUAL, MATH>(p, s);
@@ -1497,6 +1499,13 @@ extern "C" int vlnce_bn_finalize_sums(double* acc, int M, int C, const float* ga
 // launches and the fp32-MFMA launches against their own peaks)
 static thread_local int g_last_path = -1;
 extern "C" int vlnce_conv2d_last_path(void) { return g_last_path; }
+// ... and which instance of it (include/vlnce_hip.h: VLNCE_CONV_KERNEL), noted by the code that picks it
+static thread_local int g_last_kernel = -1;
+extern "C" int vlnce_conv2d_last_kernel(void) { return g_last_kernel; }
+void vlnce_detail::note_conv_kernel(int value) { g_last_kernel = value; }
+static void note_f32_kernel(int kernel, int a = 0) {
+  g_last_kernel = VLNCE_CONV_KERNEL(VLNCE_CONV_PATH_F32, 0, kernel, a, 0, 0);
+}
 
 extern "C" int vlnce_conv2d_fwd(const float* x, const float* w, float* y, const vlnce_conv_desc* d,
                                 const vlnce_prologue* pro, const vlnce_epilogue* epi,
@@ -1604,6 +1613,7 @@ extern "C" int vlnce_conv2d_fwd(const float* x, const float* w, float* y, const 
     g_last_path = VLNCE_CONV_PATH_X3;
     if (X3Plan t; x3_plan(p, &t)) return bn_sums_behind(dispatch_x3<1>(p, t, s));
     g_last_path = VLNCE_CONV_PATH_F32;
+    note_f32_kernel(VLNCE_CONV_KERNEL_F32_DUAL);
     bn_to_partials();
     return bn_finalize_behind(dispatch_dual(p, s));
   }
@@ -1632,6 +1642,7 @@ extern "C" int vlnce_conv2d_fwd(const float* x, const float* w, float* y, const 
       p.stat_partial = nullptr;
       p.act = 0;
       p.splitk = sk;
+      note_f32_kernel(VLNCE_CONV_KERNEL_F32_SPLITK, sk);
       vlnce_zero(y, M, p.N, p.ldc, s);
       if (int rc = dispatch_small<A_BUF, B_BUF>(p, s)) return rc;
       if (stat_partial) {  // statistics of the RAW sums, as the one-pass kernels' epilogues take them
@@ -1658,10 +1669,15 @@ extern "C" int vlnce_conv2d_fwd(const float* x, const float* w, float* y, const 
     g_last_path = VLNCE_CONV_PATH_X3;
     if (X3Plan t; x3_plan(p, &t)) return bn_sums_behind(dispatch_x3<0>(p, t, s));
     g_last_path = VLNCE_CONV_PATH_F32;
+    note_f32_kernel(VLNCE_CONV_KERNEL_F32_BUF);
     bn_to_partials();
     return bn_finalize_behind(dispatch_tiles<A_BUF, B_BUF>(p, s));
   }
   bn_to_partials();
+  note_f32_kernel(v4 ? VLNCE_CONV_KERNEL_F32_V4
+                  : d->KW == 7 && d->Cin == 3 ? VLNCE_CONV_KERNEL_F32_STEM3
+                  : d->KW == 7 && d->Cin == 1 ? VLNCE_CONV_KERNEL_F32_STEM1
+                                              : VLNCE_CONV_KERNEL_F32_S);
   if (v4) return bn_finalize_behind(dispatch_tiles<A_IM2COL_V4, B_NK_V4>(p, s));
   if (d->KW == 7 && d->Cin == 3) return bn_finalize_behind(dispatch_stem<3>(p, s));
   if (d->KW == 7 && d->Cin == 1) return bn_finalize_behind(dispatch_stem<1>(p, s));
@@ -1754,6 +1770,14 @@ extern "C" int vlnce_gemm(const float* A, int lda, int transA, const float* B, i
 
 static thread_local int g_wgrad_last_path = -1;
 extern "C" int vlnce_conv2d_wgrad_last_path(void) { return g_wgrad_last_path; }
+// ... and which instance (VLNCE_WGRAD_KERNEL): the row tile and the split are noted by the launcher
+static thread_local int g_wgrad_tm = 0, g_wgrad_split = 0;
+static thread_local int g_wgrad_last_kernel = -1;
+extern "C" int vlnce_conv2d_wgrad_last_kernel(void) { return g_wgrad_last_kernel; }
+void vlnce_detail::note_wgrad_kernel(int tm, bool split) {
+  g_wgrad_tm = tm;
+  g_wgrad_split = split;
+}
 
 // dW[Cout, KH, KW, Cin] = sum over output pixels of dY[m, co] * im2col(X)[m, (r,q,ci)]
 extern "C" int vlnce_conv2d_wgrad(const float* x, const float* dy, float* dw_ohwi,
@@ -1791,6 +1815,7 @@ extern "C" int vlnce_conv2d_wgrad(const float* x, const float* dy, float* dw_ohw
     if (const int rc = wgrad_x6_try_launch(x, dy, dw_ohwi, d, dy_pow2, dy_pow2 ? dy_pow2 + P : nullptr,
                                            accumulate, reinterpret_cast<hipStream_t>(stream)); rc >= 0) {
       g_wgrad_last_path = dy_pow2 ? VLNCE_WGRAD_PATH_X6_F16 : VLNCE_WGRAD_PATH_X6_BF16;
+      g_wgrad_last_kernel = VLNCE_WGRAD_KERNEL(g_wgrad_last_path, g_wgrad_tm, g_wgrad_split);
       return rc;
     }
   g_wgrad_last_path = VLNCE_WGRAD_PATH_F32;
@@ -1806,6 +1831,7 @@ extern "C" int vlnce_conv2d_wgrad(const float* x, const float* dy, float* dw_ohw
   if (sk > KT / 4) sk = KT / 4;
   if (sk > 512) sk = 512;
   p.splitk = sk < 2 ? 1 : (int)sk;
+  g_wgrad_last_kernel = VLNCE_WGRAD_KERNEL(VLNCE_WGRAD_PATH_F32, T, p.splitk > 1);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (p.splitk > 1) {
     if (!accumulate) vlnce_zero(dw_ohwi, 1, p.M * p.N, (long)p.M * p.N, s);

@@ -475,4 +475,10 @@ int wgrad_x6_try_launch(const float* x, const float* dy, float* dw, const vlnce_
                         const float* dy_up, const float* dy_down, int accumulate,
                         hipStream_t stream);
 
+// igemm.hip: the record behind vlnce_conv2d_last_kernel / vlnce_conv2d_wgrad_last_kernel (thread-local).
+// Called by whoever picks the template instance, with VLNCE_CONV_KERNEL(...) of include/vlnce_hip.h;
+// for the weight gradient with the row tile and whether the reduction was split.
+void note_conv_kernel(int value);
+void note_wgrad_kernel(int tm, bool split);
+
 }  // namespace vlnce_detail

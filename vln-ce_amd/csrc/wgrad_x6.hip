@@ -295,6 +295,7 @@ int launch_w6(const WgradParams& p0, hipStream_t stream) {
   if (sk > 65535) sk = 65535;
   p.chunks_per_slice = ceil_div(chunks, sk);
   sk = ceil_div(chunks, p.chunks_per_slice);
+  note_wgrad_kernel(TM, sk > 1);
   if (sk > 1 && !p.accumulate)
     vlnce_zero(p.dw, 1, (int)((long)p.Cout * p.K), (long)p.Cout * p.K, stream);
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)sk), dim3(512), smem, stream, p);
