@@ -39,6 +39,7 @@ class _WeightCache:
         self._packed = {}
         self._folded = {}
         self._prep = None
+        self._convs = None
 
     @staticmethod
     def _key(*ts):
@@ -55,14 +56,17 @@ class _WeightCache:
             self._packed[id(conv)] = hit
         return hit[1]
 
-    def prepare_trainable(self, convs):
-        """Trainable trunks: every weight image the step needs -- OHWI fp32, planes and fragments in
+    def prepare_trainable(self, trunk):
+        """Trainable trunks, over all convolutions of `trunk`: every weight image the step needs --
+        OHWI fp32, planes and fragments in
         the forward format, and the data-gradient bank (taps reversed, channels swapped) as fp32,
         planes and fragments in the backward format (ops.GRAD_PLANES) -- written by ONE launch (vlnce_conv2d_prepare_weights)
         into persistent buffers, and handed to conv() / ops.split_weights / ops.pack_weights /
         trunk_backward.conv_backward through the caches those already consult.  Convolutions the
         kernel does not take (the stems: Cin = 1 or 3) keep the per-tensor path."""
-        convs = [c for c in convs if c.weight.is_cuda and c.weight.is_contiguous()
+        if self._convs is None:
+            self._convs = [m for m in trunk.modules() if isinstance(m, nn.Conv2d)]
+        convs = [c for c in self._convs if c.weight.is_cuda and c.weight.is_contiguous()
                  and c.weight.size(0) % 32 == 0 and c.weight.size(1) % 32 == 0]
         if not convs or os.environ.get("VLNCE_WEIGHT_PREP", "1") == "0":
             return
@@ -413,7 +417,7 @@ class HipResNetTrunk(DropsGraphsOnApply, nn.Sequential):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._plist()):
             # trainable encoder: layer-by-layer forward that records what backward needs
             x = ops.frames_f32(ops.frames(x_nhwc_raw))
-            return tb.TrunkFn.apply(self, x, *self.trainable_params()).permute(0, 3, 1, 2)
+            return tb.TrunkFn.apply(self, x, *tb.trainable_params(self)).permute(0, 3, 1, 2)
         key, train = self._graph_key(ops.frames_signature(x_nhwc_raw))
         y = self._graphs(x_nhwc_raw, key)
         if train:
@@ -490,110 +494,20 @@ class HipResNetTrunk(DropsGraphsOnApply, nn.Sequential):
 
 
     # ------------------------------------------------------------------ trainable mode
-    def trainable_params(self):
-        return [p for p in self.parameters() if p.requires_grad]
-
-    def _all_convs(self):
-        if getattr(self, "_conv_list", None) is None:
-            self._conv_list = [m for m in self.modules() if isinstance(m, nn.Conv2d)]
-        return self._conv_list
-
-    def _rec_conv_bn(self, x, conv, bn, relu, residual, tape, touched):
-        w = self._cache.conv(conv)
-        stride, pad = conv.stride[0], conv.padding[0]
-        if bn.training:
-            raw, stats = ops.conv2d_nhwc(x, w, stride, pad, want_stats=True)
-        else:
-            raw, stats = ops.conv2d_nhwc(x, w, stride, pad), None
-        y, sv = tb.bn_forward(raw, bn, relu, residual, stats, touched)
-        tape.append(("conv_bn", x, conv, bn, w, sv))
-        return y
-
     def run_recording(self, x):
         kids = list(self.children())
-        tape, touched = [], []
-        self._cache.prepare_trainable(self._all_convs())
+        self._cache.prepare_trainable(self)
         sc, sh = self.input_scale
         x = ops.scale_shift_act(x, sc, sh)  # /255 (+mean/std) materialised: wgrad reads it
-        x = self._rec_conv_bn(x, kids[0], kids[1], True, None, tape, touched)
-        x, saved = tb.maxpool_forward(x)
-        tape.append(("maxpool", saved))
-        for stage in kids[4:8]:
-            for blk in stage:
-                block_in = x
-                identity = x
-                tape.append(("block_begin", blk.downsample is not None))
-                if blk.downsample is not None:
-                    identity = self._rec_conv_bn(block_in, blk.downsample[0], blk.downsample[1],
-                                                 False, None, tape, touched)
-                tape.append(("main_begin",))
-                st = blk.stages()
-                cur = block_in
-                for conv, bn in st[:-1]:
-                    cur = self._rec_conv_bn(cur, conv, bn, True, None, tape, touched)
-                x = self._rec_conv_bn(cur, st[-1][0], st[-1][1], True, identity, tape, touched)
-                tape.append(("block_end",))
-        for pool in kids[8:]:
-            tape.append(("avgpool", tuple(x.shape), pool.out_hw))
-            x = ops.adaptive_avgpool(x, *pool.out_hw)
+        blocks = [(None if blk.downsample is None else tuple(blk.downsample), blk.stages())
+                  for stage in kids[4:8] for blk in stage]
+        x, tape, touched = tb.record(x, self._cache.conv, (kids[0], kids[1]), blocks,
+                                     [("avgpool", pool.out_hw) for pool in kids[8:]])
         if touched:
             torch._foreach_add_(touched, 1)
         if any(m.training for m in self._norms):
             self._bn_gen += 1
         return x, tape
-
-    def backward_from_tape(self, tape, dout):
-        """Replays the tape in reverse.  Block structure on the tape:
-        block_begin, [downsample conv_bn], main_begin, conv_bn*, block_end."""
-        grads = {}
-
-        def conv_bn_back(entry, dy, need_dx=True, add=None):
-            _, x_in, conv, bn, w, sv = entry
-            draw, dres, dg, db, pow2 = tb.bn_backward(
-                dy, sv, max(conv.in_channels, conv.out_channels) if need_dx else 4)
-            dx, dw = tb.conv_backward(x_in, w, draw, conv.stride[0], conv.padding[0], need_dx, add,
-                                      pow2)
-            for prm, g in ((conv.weight, dw), (bn.weight, dg), (bn.bias, db)):
-                if prm.requires_grad:
-                    grads[id(prm)] = g
-            return dx, dres
-
-        i = len(tape) - 1
-        d = dout
-        while i >= 0:
-            kind = tape[i][0]
-            if kind == "avgpool":
-                d = tb.avgpool_backward(d, tape[i][1], tape[i][2])
-                i -= 1
-            elif kind == "block_end":
-                # main path convs back to main_begin
-                i -= 1
-                d_main, d_skip = conv_bn_back(tape[i], d)  # last conv: residual gradient
-                i -= 1
-                # the two branches' gradients meet at the block input: the LAST data-gradient
-                # convolution issued for the block adds the other branch in its epilogue
-                while tape[i][0] != "main_begin":
-                    first = tape[i - 1][0] == "main_begin"
-                    plain_skip = first and tape[i - 2][0] != "conv_bn"
-                    d_main, _ = conv_bn_back(tape[i], d_main, add=d_skip if plain_skip else None)
-                    i -= 1
-                i -= 1  # past main_begin
-                if tape[i][0] == "conv_bn":  # downsample branch
-                    d, _ = conv_bn_back(tape[i], d_skip, add=d_main)
-                    i -= 1
-                else:
-                    d = d_main
-                assert tape[i][0] == "block_begin"
-                i -= 1
-            elif kind == "maxpool":
-                d = tb.maxpool_backward(d, tape[i][1])
-                i -= 1
-            elif kind == "conv_bn":  # the stem: its input is the image, no data gradient
-                conv_bn_back(tape[i], d, need_dx=False)
-                i -= 1
-            else:
-                raise AssertionError(kind)
-        return grads
 
 
 _TV_CHILD_INDEX = {"conv1": "0", "bn1": "1", "layer1": "4", "layer2": "5", "layer3": "6",
@@ -724,7 +638,15 @@ class TorchVisionResNet18(TorchVisionResNet):
 
 
 # ------------------------------------------------------------------ habitat GroupNorm trunk
-class GNBasicBlock(nn.Module):
+class _GNBlock(nn.Module):
+    def stages(self):
+        """convs = [conv, GN, ReLU]* + [conv, GN] as (conv, gn) pairs; the last GroupNorm output
+        gets the skip connection added and then the block's ReLU."""
+        mods = [m for m in self.convs if not isinstance(m, nn.ReLU)]
+        return list(zip(mods[0::2], mods[1::2]))
+
+
+class GNBasicBlock(_GNBlock):
     expansion = 1
 
     def __init__(self, inplanes, planes, ngroups, stride=1, downsample=None):
@@ -736,7 +658,7 @@ class GNBasicBlock(nn.Module):
         self.relu = nn.ReLU(True)
 
 
-class GNBottleneck(nn.Module):
+class GNBottleneck(_GNBlock):
     expansion = 4
 
     def __init__(self, inplanes, planes, ngroups, stride=1, downsample=None):
@@ -825,26 +747,11 @@ class HipResNetEncoder(DropsGraphsOnApply, nn.Module):
                                        residual=residual,
                                        act=ops.ACT_RELU if relu else ops.ACT_NONE)
 
-    def _run_convs(self, x, seq, residual):
-        """block.convs = [conv, GN, ReLU]* + [conv, GN]; the last GroupNorm output gets
-        the skip connection added and then the block's ReLU."""
-        mods, pairs, i = list(seq), [], 0
-        while i < len(mods):
-            relu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.ReLU)
-            pairs.append((mods[i], mods[i + 1], relu))
-            i += 3 if relu else 2
-        for j, (conv, gn, relu) in enumerate(pairs):
-            if j == len(pairs) - 1:
-                x = self._conv_gn(x, conv, gn, True, residual=residual)
-            else:
-                x = self._conv_gn(x, conv, gn, relu)
-        return x
-
     def forward(self, observations):
         x = observations["depth"]  # [B,H,W,1] channels-last already; or the ops.frames tuple
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._plist()):
             x = ops.frames_f32(ops.frames(x))
-            return tb.TrunkFn.apply(self, x, *self.trainable_params()).permute(0, 3, 1, 2)
+            return tb.TrunkFn.apply(self, x, *tb.trainable_params(self)).permute(0, 3, 1, 2)
         return self._graphs(x, self._graph_key(ops.frames_signature(x))).permute(0, 3, 1, 2)
 
     def _graph_key(self, signature):
@@ -864,107 +771,22 @@ class HipResNetEncoder(DropsGraphsOnApply, nn.Module):
                     identity = x
                     if blk.downsample is not None:
                         identity = self._conv_gn(x, blk.downsample[0], blk.downsample[1], False)
-                    x = self._run_convs(x, blk.convs, identity)
+                    st = blk.stages()
+                    for conv, gn in st[:-1]:
+                        x = self._conv_gn(x, conv, gn, True)
+                    x = self._conv_gn(x, st[-1][0], st[-1][1], True, residual=identity)
             x = self._conv_gn(x, self.compression[0], self.compression[1], True)
         return x
 
-
-# ---- trainable mode of HipResNetEncoder (methods attached below the class for readability)
-def _depth_trainable_params(self):
-    return [p for p in self.parameters() if p.requires_grad]
-
-
-def _depth_rec_conv_gn(self, x, conv, gn, relu, residual, tape):
-    w = self._cache.conv(conv)
-    raw = ops.conv2d_nhwc(x, w, conv.stride[0], conv.padding[0])
-    y, sv = tb.gn_forward(raw, gn, relu, residual)
-    tape.append(("conv_gn", x, conv, gn, w, sv))
-    return y
-
-
-def _depth_run_recording(self, x):
-    tape = []
-    if getattr(self, "_conv_list", None) is None:
-        self._conv_list = [m for m in self.modules() if isinstance(m, nn.Conv2d)]
-    self._cache.prepare_trainable(self._conv_list)
-    x = ops.avgpool2x2(x)
-    bb = self.backbone
-    x = self._rec_conv_gn(x, bb.conv1[0], bb.conv1[1], True, None, tape)
-    x, saved = tb.maxpool_forward(x)
-    tape.append(("maxpool", saved))
-    for stage in (bb.layer1, bb.layer2, bb.layer3, bb.layer4):
-        for blk in stage:
-            block_in, identity = x, x
-            tape.append(("block_begin",))
-            if blk.downsample is not None:
-                identity = self._rec_conv_gn(block_in, blk.downsample[0], blk.downsample[1], False,
-                                             None, tape)
-            tape.append(("main_begin",))
-            mods, pairs, i = list(blk.convs), [], 0
-            while i < len(mods):
-                relu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.ReLU)
-                pairs.append((mods[i], mods[i + 1]))
-                i += 3 if relu else 2
-            cur = block_in
-            for conv, gn in pairs[:-1]:
-                cur = self._rec_conv_gn(cur, conv, gn, True, None, tape)
-            x = self._rec_conv_gn(cur, pairs[-1][0], pairs[-1][1], True, identity, tape)
-            tape.append(("block_end",))
-    x = self._rec_conv_gn(x, self.compression[0], self.compression[1], True, None, tape)
-    return x, tape
-
-
-def _depth_backward_from_tape(self, tape, dout):
-    grads = {}
-
-    def back(entry, dy, need_dx=True, add=None):
-        _, x_in, conv, gn, w, sv = entry
-        draw, dres, dg, db, pow2 = tb.gn_backward(
-            dy, sv, max(conv.in_channels, conv.out_channels) if need_dx else 4)
-        dx, dw = tb.conv_backward(x_in, w, draw, conv.stride[0], conv.padding[0], need_dx, add, pow2)
-        for prm, g in ((conv.weight, dw), (gn.weight, dg), (gn.bias, db)):
-            if prm.requires_grad:
-                grads[id(prm)] = g
-        return dx, dres
-
-    i = len(tape) - 1
-    d = dout
-    while i >= 0:
-        kind = tape[i][0]
-        if kind == "block_end":
-            i -= 1
-            d_main, d_skip = back(tape[i], d)
-            i -= 1
-            while tape[i][0] != "main_begin":   # (block-input sum in an epilogue: see the RGB trunk)
-                first = tape[i - 1][0] == "main_begin"
-                plain_skip = first and tape[i - 2][0] != "conv_gn"
-                d_main, _ = back(tape[i], d_main, add=d_skip if plain_skip else None)
-                i -= 1
-            i -= 1
-            if tape[i][0] == "conv_gn":
-                d, _ = back(tape[i], d_skip, add=d_main)
-                i -= 1
-            else:
-                d = d_main
-            assert tape[i][0] == "block_begin"
-            i -= 1
-        elif kind == "maxpool":
-            d = tb.maxpool_backward(d, tape[i][1])
-            i -= 1
-        elif kind == "conv_gn":
-            # compression conv (has a data gradient) or the stem (input is the depth image)
-            is_stem = i == 0
-            d, _ = back(tape[i], d, need_dx=not is_stem)
-            i -= 1
-        else:
-            raise AssertionError(kind)
-    return grads
-
-
-HipResNetEncoder.trainable_params = _depth_trainable_params
-HipResNetEncoder._rec_conv_gn = _depth_rec_conv_gn
-HipResNetEncoder.run_recording = _depth_run_recording
-HipResNetEncoder.backward_from_tape = _depth_backward_from_tape
+    # ---- trainable mode (the walk itself: trunk_backward.record / backward_from_tape)
+    def run_recording(self, x):
+        self._cache.prepare_trainable(self)
+        bb = self.backbone
+        blocks = [(None if blk.downsample is None else tuple(blk.downsample), blk.stages())
+                  for stage in (bb.layer1, bb.layer2, bb.layer3, bb.layer4) for blk in stage]
+        x, tape, _ = tb.record(ops.avgpool2x2(x), self._cache.conv, (bb.conv1[0], bb.conv1[1]),
+                               blocks, [(self.compression[0], self.compression[1])])
+        return x, tape
 
 
 def single_frame_box_shape(box):

@@ -3,7 +3,10 @@
 The frozen (default) trunks run a fused forward-only plan (resnet_encoders.py).
 With trainable encoders the trunk runs layer by layer, keeps the raw conv
 outputs and the normalised activations, and this module's `TrunkFn` replays the
-layers in reverse on the hand-written backward kernels:
+layers in reverse on the hand-written backward kernels.  Both trunks (BatchNorm
+RGB, GroupNorm depth) share one recorder and one replayer, `record` and
+`backward_from_tape` below; a trunk module supplies its layer description
+(stem, blocks, tail) and keeps its input preparation and bookkeeping:
 
   conv  : data gradient  = vlnce_conv2d_fwd with the flipped/transposed weights
                            (stride-2 3x3: zero-inserted dY; stride-2 1x1: strided scatter)
@@ -14,6 +17,7 @@ layers in reverse on the hand-written backward kernels:
 import os
 
 import torch
+import torch.nn as nn
 from torch.autograd import Function
 
 from .. import ops
@@ -27,10 +31,6 @@ _SEPARATE_ADD = os.environ.get("VLNCE_DGRAD_ADD", "1") == "0"
 
 
 # ------------------------------------------------------------------ layer primitives
-def conv_raw(x, w_ohwi, stride, pad):
-    return ops.conv2d_nhwc(x, w_ohwi, stride, pad)
-
-
 def conv_backward(x, w_ohwi, dy, stride, pad, need_dx, add=None, pow2=None):
     """returns (dx | None, dW in OIHW).  `add` (the gradient arriving at the same tensor over the
     block's other branch) is summed into dx by the data-gradient convolution's epilogue instead of
@@ -223,12 +223,118 @@ def avgpool_backward(dy, in_shape, out_hw):
     return dx
 
 
-# ------------------------------------------------------------------ the trunk Function
+# ------------------------------------------------------------------ recording and replay
+def trainable_params(trunk):
+    return [p for p in trunk.parameters() if p.requires_grad]
+
+
+def record(x, weights, stem, blocks, tail):
+    """Runs a trunk layer by layer on its prepared input `x`; returns (out, tape, touched).
+    `weights(conv)` gives the OHWI weights; `stem` is (conv, norm); `blocks` is a flat list of
+    (downsample (conv, norm) | None, [(conv, norm), ...]) in forward order; `tail` lists what
+    follows the last block, ("avgpool", out_hw) or (conv, norm).  The norm kind is the module's
+    type; `touched` collects the num_batches_tracked of every train-mode BatchNorm.
+    Block structure on the tape: block_begin, [downsample conv_norm], main_begin, conv_norm*,
+    block_end."""
+    tape, touched = [], []
+
+    def layer(x, conv, norm, relu, residual=None):
+        w = weights(conv)
+        stride, pad = conv.stride[0], conv.padding[0]
+        if isinstance(norm, nn.GroupNorm):
+            y, sv = gn_forward(ops.conv2d_nhwc(x, w, stride, pad), norm, relu, residual)
+        else:
+            assert isinstance(norm, nn.BatchNorm2d), type(norm)
+            if norm.training:
+                raw, stats = ops.conv2d_nhwc(x, w, stride, pad, want_stats=True)
+            else:
+                raw, stats = ops.conv2d_nhwc(x, w, stride, pad), None
+            y, sv = bn_forward(raw, norm, relu, residual, stats, touched)
+        tape.append(("conv_norm", x, conv, norm, w, sv))
+        return y
+
+    x = layer(x, *stem, True)
+    x, saved = maxpool_forward(x)
+    tape.append(("maxpool", saved))
+    for down, main in blocks:
+        tape.append(("block_begin",))
+        identity = x if down is None else layer(x, *down, False)
+        tape.append(("main_begin",))
+        cur = x
+        for conv, norm in main[:-1]:
+            cur = layer(cur, conv, norm, True)
+        x = layer(cur, *main[-1], True, identity)
+        tape.append(("block_end",))
+    for t in tail:
+        if t[0] == "avgpool":
+            tape.append(("avgpool", tuple(x.shape), t[1]))
+            x = ops.adaptive_avgpool(x, *t[1])
+        else:
+            x = layer(x, *t, True)
+    return x, tape, touched
+
+
+def backward_from_tape(tape, dout):
+    """Replays the tape in reverse; returns {id(param): gradient} for parameters with
+    requires_grad."""
+    grads = {}
+
+    def back(entry, dy, need_dx=True, add=None):
+        _, x_in, conv, norm, w, sv = entry
+        norm_backward = bn_backward if isinstance(sv, BNSaved) else gn_backward
+        draw, dres, dg, db, pow2 = norm_backward(
+            dy, sv, max(conv.in_channels, conv.out_channels) if need_dx else 4)
+        dx, dw = conv_backward(x_in, w, draw, conv.stride[0], conv.padding[0], need_dx, add, pow2)
+        for prm, g in ((conv.weight, dw), (norm.weight, dg), (norm.bias, db)):
+            if prm.requires_grad:
+                grads[id(prm)] = g
+        return dx, dres
+
+    i = len(tape) - 1
+    d = dout
+    while i >= 0:
+        kind = tape[i][0]
+        if kind == "avgpool":
+            d = avgpool_backward(d, tape[i][1], tape[i][2])
+            i -= 1
+        elif kind == "block_end":
+            # main path convs back to main_begin
+            i -= 1
+            d_main, d_skip = back(tape[i], d)  # last conv: residual gradient
+            i -= 1
+            # the two branches' gradients meet at the block input: the LAST data-gradient
+            # convolution issued for the block adds the other branch in its epilogue
+            while tape[i][0] != "main_begin":
+                first = tape[i - 1][0] == "main_begin"
+                plain_skip = first and tape[i - 2][0] != "conv_norm"
+                d_main, _ = back(tape[i], d_main, add=d_skip if plain_skip else None)
+                i -= 1
+            i -= 1  # past main_begin
+            if tape[i][0] == "conv_norm":  # downsample branch
+                d, _ = back(tape[i], d_skip, add=d_main)
+                i -= 1
+            else:
+                d = d_main
+            assert tape[i][0] == "block_begin"
+            i -= 1
+        elif kind == "maxpool":
+            d = maxpool_backward(d, tape[i][1])
+            i -= 1
+        elif kind == "conv_norm":
+            # outside a block: a tail conv (has a data gradient) or the stem, tape entry 0,
+            # whose input is the image
+            d, _ = back(tape[i], d, need_dx=i != 0)
+            i -= 1
+        else:
+            raise AssertionError(kind)
+    return grads
+
+
 class TrunkFn(Function):
-    """forward(plan, x, *params): plan.run(x) -> (out, tape); backward replays the tape.
-    `plan` is the owning trunk module (it knows its layer structure); `params` are its
-    trainable parameters in `plan.trainable_params()` order so autograd routes the
-    returned gradients to them."""
+    """forward(plan, x, *params): plan.run_recording(x) -> (out, tape); backward replays the
+    tape.  `plan` is the owning trunk module (it knows its layer structure); `params` are its
+    trainable parameters in `trainable_params(plan)` order so autograd routes the returned
+    gradients to them."""
 
     @staticmethod
     def forward(ctx, plan, x, *params):
@@ -240,7 +346,7 @@ class TrunkFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        grads = ctx.plan.backward_from_tape(ctx.tape, dout.contiguous())
+        grads = backward_from_tape(ctx.tape, dout.contiguous())
         ctx.tape = None
-        plist = ctx.plan.trainable_params()
+        plist = trainable_params(ctx.plan)
         return (None, None) + tuple(grads.get(id(p)) for p in plist)
