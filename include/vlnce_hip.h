@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 146 = this header */
+int vlnce_version(void); /* major*100 + minor; 147 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -766,6 +766,46 @@ int vlnce_ragged_pad_rows_i64(const int64_t* src, const int* offsets, int B, int
 int vlnce_dagger_targets(const int64_t* oracle_actions, const int* offsets, int B, int Tmax,
                          float inflection_coef, int64_t* corrected_out, float* weights_out,
                          uint8_t* masks_out, vlnce_stream_t stream);
+
+/* ---- DAgger rollout collection (ABI 147): the WRITE half of the feature cache ---------------
+ * What dagger_trainer.py:294-314 (feature hooks: o.cpu() per step), :420-435 (per-environment
+ * .item() read-backs) and :339-356 (host re-stack + astype(float16) per finished episode) do on
+ * the host, kept on the device: every recorded sensor has an arena [num_envs][capacity][C*P] in
+ * its STORAGE dtype, and one launch appends one step of every sensor for every live environment.
+ * Source row r of a sensor goes to dst + ((long)slots[r]*capacity + steps[r]) * C*P, c-major
+ * (NCHW order) whatever the source's strides -- the trunks hand out a permuted NHWC view (c_stride
+ * 1, p_stride C), read coalesced along c, each lane writing its P outputs contiguously; contiguous
+ * sources (P = 1, c_stride 1) move 4 elements per lane where pointers, row_stride and C allow.
+ * ONLY P = 16 and P = 4 (the 4x4 and 2x2 maps of the cached trunks) with c_stride 1 take that
+ * transposed path; any other strided view (P = 49, P = 8, c_stride > 1, ...) is correct but goes one
+ * output element per lane: coalesced stores, loads strided by p_stride across the wave.
+ * Conversions: f32 -> f16 rounds to nearest even, subnormals kept, overflow to infinity (numpy's
+ * astype(float16)); i64 -> f16 goes through f32 (batch_obs casts to float first); u8 -> f16 / f32
+ * and same-type copies are exact; f32 / u8 -> i64 truncate like a C cast.
+ * sensors / slots / steps are HOST arrays copied into the launch arguments: no H2D copy, no
+ * allocation, no synchronisation.  At most VLNCE_TRAJ_MAX_SENSORS sensors and VLNCE_TRAJ_MAX_ROWS
+ * rows per call (more: error; the caller splits); every steps[r] in [0, capacity), slots[r] >= 0
+ * (the arena's first extent is the caller's to respect).  All index arithmetic is 64-bit. */
+enum { VLNCE_TRAJ_F32 = 0, VLNCE_TRAJ_F16 = 1, VLNCE_TRAJ_I64 = 2, VLNCE_TRAJ_U8 = 3 };
+#define VLNCE_TRAJ_MAX_SENSORS 8
+#define VLNCE_TRAJ_MAX_ROWS 128
+typedef struct {
+  const void* src;      /* element (row r, c, p) at src + (r*row_stride + c*c_stride + p*p_stride) * elem */
+  void* dst;            /* arena [num_envs][capacity][C*P] in the storage dtype                            */
+  long row_stride, c_stride, p_stride;   /* in elements of the source dtype, >= 0                         */
+  int C, P;             /* a row is written as C*P contiguous elements, c-major (NCHW order)              */
+  int src_dtype;        /* VLNCE_TRAJ_F32 | _I64 | _U8                                                     */
+  int dst_dtype;        /* VLNCE_TRAJ_F16 | _F32 | _I64                                                    */
+} vlnce_traj_sensor;
+int vlnce_traj_append(const vlnce_traj_sensor* sensors, int n_sensors, const int* slots,
+                      const int* steps, int n_rows, long capacity, vlnce_stream_t stream);
+/* dagger_trainer.py:414-442 in one launch, per row: e = (long)expert; a = uniform < beta ? e :
+ * action (fp32 comparison, as torch compares with a Python float); skip = (e == -1); a = skip ? 0
+ * : a; prev_actions = a; stepped = {a, skip}.  expert_dtype: VLNCE_TRAJ_F32 | VLNCE_TRAJ_I64.
+ * `uniform` is the caller's torch.rand_like(actions, dtype=float): the RNG stream stays torch's. */
+int vlnce_dagger_mix_actions(const int64_t* actions, const void* expert, int expert_dtype,
+                             const float* uniform, float beta, int n, int64_t* prev_actions,
+                             int64_t* stepped /* [2][n] */, vlnce_stream_t stream);
 
 /* DD-PPO returns: RolloutStorage.compute_returns (rollout_storage.py:127-152).
  * rewards [T,N]; value_preds, masks, returns [T+1,N]; next_value [N].  GAE: value_preds[T] is set

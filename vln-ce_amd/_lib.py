@@ -98,6 +98,11 @@ class BnSums(C.Structure):
     _fields_ = [("acc", _P), ("workspace", _P), ("workspace_bytes", _L)]
 
 
+class TrajSensor(C.Structure):   # vlnce_traj_sensor
+    _fields_ = [("src", _P), ("dst", _P), ("row_stride", _L), ("c_stride", _L), ("p_stride", _L),
+                ("C", _I), ("P", _I), ("src_dtype", _I), ("dst_dtype", _I)]
+
+
 class Epilogue(C.Structure):
     _fields_ = [("scale", _P), ("shift", _P), ("residual", _P), ("ldr", _I), ("act", _I),
                 ("accumulate", _I), ("stat_partial", _P), ("bn", C.POINTER(BnSums))]
@@ -141,6 +146,8 @@ _SIGNATURES = {
     "vlnce_ragged_pad_rows": (_I, [_P, _I, _P, _I, _I, _L, _F, _P, _P]),
     "vlnce_ragged_pad_rows_i64": (_I, [_P, _P, _I, _I, _L, _L, _P, _P]),
     "vlnce_dagger_targets": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P]),
+    "vlnce_traj_append": (_I, [C.POINTER(TrajSensor), _I, C.POINTER(_I), C.POINTER(_I), _I, _L, _P]),
+    "vlnce_dagger_mix_actions": (_I, [_P, _P, _I, _P, _F, _I, _P, _P, _P]),
     "vlnce_ppo_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _F, _F, _I,
                             _P, _P, _P]),
     "vlnce_ppo_returns": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _F, _I, _P]),
@@ -202,6 +209,31 @@ _SIGNATURES = {
     "vlnce_select_rows": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "vlnce_act_bwd": (_I, [_P, _P, _P, _L, _I, _P]),
 }
+
+
+def collapse_rows(t):
+    """a source of traj_append, [n, ...], as the strided form [n, C, P] the kernel reads:
+    (tensor, row_stride, C, c_stride, P, p_stride), strides in elements.  The dimensions behind
+    the first are merged where they are contiguous with each other; what does not come down to
+    two groups (c outer, p inner, in the row's own NCHW order) is made contiguous first."""
+    while True:
+        groups = []
+        for n, st in zip(t.shape[1:], t.stride()[1:]):
+            if n == 1:
+                continue
+            if groups and groups[-1][1] == st * n:
+                groups[-1] = (groups[-1][0] * n, int(st))
+            else:
+                groups.append((int(n), int(st)))
+        if len(groups) <= 2:
+            break
+        t = t.contiguous()
+    row_stride = int(t.stride(0)) if t.size(0) > 1 else 0
+    if not groups:
+        return t, row_stride, 1, 0, 1, 0
+    if len(groups) == 1:
+        return t, row_stride, groups[0][0], groups[0][1], 1, 0
+    return t, row_stride, groups[0][0], groups[0][1], groups[1][0], groups[1][1]
 
 
 def exported_symbols():
@@ -274,7 +306,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 146  # include/vlnce_hip.h
+    ABI = 147  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -583,6 +615,62 @@ class HipLib:
         self._check(self.dll.vlnce_dagger_targets(
             _ptr(oracle), _ptr(offsets), B, Tmax, float(coef), _ptr(corrected),
             _ptr(weights), _ptr(masks), _stream()), "vlnce_dagger_targets")
+
+    # ---- DAgger rollout collection (csrc/traj.hip)
+    _TRAJ = {torch.float32: 0, torch.float16: 1, torch.int64: 2, torch.uint8: 3}
+    TRAJ_MAX_SENSORS, TRAJ_MAX_ROWS = 8, 128
+
+    def traj_append(self, sources, arenas, slots, steps):
+        """one step of every sensor: row r of sources[k] ([n, ...], f32 | i64 | u8, any strides)
+        -> arenas[k][slots[r], steps[r]] ([num_envs, capacity, D] contiguous, f16 | f32 | i64), in
+        the row's own (NCHW) element order.  slots / steps: host sequences of ints.  More than 8
+        sensors or 128 rows go out as several launches."""
+        n = len(slots)
+        assert len(sources) == len(arenas) and len(steps) == n and n > 0
+        capacity, num_envs = int(arenas[0].size(1)), min(int(a.size(0)) for a in arenas)
+        if min(slots) < 0 or max(slots) >= num_envs:
+            raise RuntimeError(f"traj_append: slot outside the arena's {num_envs} environments")
+        table, keep = [], []
+        for src, dst in zip(sources, arenas):
+            src, rs, Cc, cs, P, ps = collapse_rows(src)
+            keep.append(src)
+            if src.size(0) != n:
+                raise RuntimeError(f"traj_append: {src.size(0)} source rows for {n} slots")
+            if dst.dim() != 3 or not dst.is_contiguous() or dst.size(1) != capacity \
+                    or dst.size(2) != Cc * P:
+                raise RuntimeError(f"traj_append: arena {tuple(dst.shape)} for rows of {Cc * P} "
+                                   f"elements at capacity {capacity}")
+            if src.dtype not in (torch.float32, torch.int64, torch.uint8) \
+                    or dst.dtype not in (torch.float16, torch.float32, torch.int64):
+                raise RuntimeError(f"traj_append: {src.dtype} -> {dst.dtype} is not a recorded pair")
+            table.append((src, dst, rs, Cc, cs, P, ps))
+        for r0 in range(0, n, self.TRAJ_MAX_ROWS):
+            r1 = min(n, r0 + self.TRAJ_MAX_ROWS)
+            sl = (_I * (r1 - r0))(*[int(v) for v in slots[r0:r1]])
+            stp = (_I * (r1 - r0))(*[int(v) for v in steps[r0:r1]])
+            for k0 in range(0, len(table), self.TRAJ_MAX_SENSORS):
+                part = table[k0:k0 + self.TRAJ_MAX_SENSORS]
+                arr = (TrajSensor * len(part))()
+                for a, (src, dst, rs, Cc, cs, P, ps) in zip(arr, part):
+                    a.src = _ptr(src) + r0 * rs * src.element_size()
+                    a.dst = _ptr(dst)
+                    a.row_stride, a.c_stride, a.p_stride, a.C, a.P = rs, cs, ps, Cc, P
+                    a.src_dtype, a.dst_dtype = self._TRAJ[src.dtype], self._TRAJ[dst.dtype]
+                self._check(self.dll.vlnce_traj_append(arr, len(part), sl, stp, r1 - r0, capacity,
+                                                       _stream()), "vlnce_traj_append")
+
+    def dagger_mix_actions(self, actions, expert, uniform, beta, prev_actions, stepped):
+        """dagger_trainer.py:414-442 per row; prev_actions [n] is overwritten, stepped [2, n] int64 =
+        {the action handed to the simulator, the skip flag}"""
+        n = actions.numel()
+        assert actions.dtype == torch.int64 and prev_actions.dtype == torch.int64
+        assert stepped.dtype == torch.int64 and stepped.numel() == 2 * n and stepped.is_contiguous()
+        assert uniform.dtype == torch.float32 and expert.dtype in (torch.float32, torch.int64)
+        assert expert.numel() == n and uniform.numel() == n and prev_actions.numel() == n
+        assert all(t.is_contiguous() for t in (actions, expert, uniform, prev_actions))
+        self._check(self.dll.vlnce_dagger_mix_actions(
+            _ptr(actions), _ptr(expert), self._TRAJ[expert.dtype], _ptr(uniform), float(beta), n,
+            _ptr(prev_actions), _ptr(stepped), _stream()), "vlnce_dagger_mix_actions")
 
     def ppo_loss(self, values, returns, value_preds, logp, old_logp, adv, ent_pano, ent_offset,
                  ent_distance, radians, B, clip, value_coef, entropy_coef, pano_coef, offset_coef,

@@ -38,7 +38,8 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // shares of dgamma / dbeta are added up in sample order (no atomics).
 // 146: vlnce_conv2d_last_kernel / vlnce_conv2d_wgrad_last_kernel (which kernel INSTANCE the thread's last
 // launch ran on: family, plane format, tile / mode / template arguments; VLNCE_CONV_KERNEL_*).
-extern "C" int vlnce_version(void) { return 146; }
+// 147: vlnce_traj_append / vlnce_traj_sensor, vlnce_dagger_mix_actions (DAgger rollout collection on the device).
+extern "C" int vlnce_version(void) { return 147; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)
