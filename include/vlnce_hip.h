@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 147 = this header */
+int vlnce_version(void); /* major*100 + minor; 148 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -61,6 +61,14 @@ const char* vlnce_last_error(void);
  *                               tile of the fp32-MFMA kernel where that one runs
  *   "rollout_one_xcd"  0        1: all workgroups of vlnce_gru_rollout_* on one XCD
  *   "m3"               1        conv_m3_kernel (small launches): 0 off, 1 default rule, 2 / 3 every layer it covers
+ *   "r3"               1        the regenerating block end (vlnce_prologue.regen, conv_r3_kernel; ABI 148).  The
+ *                               library launches what a call asks for; the HOST reads this option to choose
+ *                               between the two routes of a block end: 0 conv3 stores its raw output and the
+ *                               next 1x1 reads it back, 1 the layers on which the regenerating pair was measured
+ *                               faster (launches of at least four 64-row tiles per CU), 2 every block end the
+ *                               kernel covers
+ *   "s3_wgs"           0        conv_s3_kernel / conv_r3_kernel: 0 = one workgroup per CU; n > 0 = at most n
+ *                               workgroups (tests: many tiles per workgroup at a small M)
  * Set options between launches, not concurrently with them (relaxed atomics).  Unknown names
  * return non-zero. */
 int vlnce_set_option(const char* name, int value);
@@ -81,6 +89,27 @@ typedef struct {
   int Ho, Wo;         /* output [N,Ho,Wo,Cout], row stride ldy floats (>= Cout) */
   int ldx, ldy;
 } vlnce_conv_desc;
+
+/* The launch's input REGENERATED instead of read (ABI 148; vlnce_prologue.regen): x of the launch
+ * would have been the raw output of the stride-1 1x1 expansion
+ *   x[m, :] = conv1x1(act((rx[m, :] - in_center) * in_scale + in_shift), w)      Cin -> 4 Cin channels
+ * and the launch computes it again, tile by tile in registers, from rx -- a quarter of the bytes --
+ * instead of reading it back.  Train-mode ResNet-50 layers 1-2: conv3 of a bottleneck runs as a
+ * statistics-only launch (vlnce_epilogue.stats_only), and the block end inside the next block's
+ * first 1x1 (dual-input prologue below) regenerates conv3's output from conv2's.  The values are
+ * those the statistics were taken from (same kernel arithmetic), so side_out is what the storing
+ * route writes.  conv_r3_kernel: Cin = 64 / 128, Cout of the launch 64 / 128 (Cin 64) or 128 / 256
+ * (Cin 128); needs x2, in_scale / in_shift (the expansion's BatchNorm), side_out, w_frag, a raw output
+ * (no epilogue arithmetic) and x == NULL.  Anything else is an error, never another kernel. */
+typedef struct {
+  const float* x;         /* rx: [N,H,W,Cin] of the launch's geometry, pixel stride ldx floats (>= Cin)  */
+  int Cin, ldx;
+  const void* w_frag;     /* the expansion's weights [4 Cin, 1, 1, Cin] as B fragments, format w_format */
+  const float* in_scale;  /* its operand prologue (NULL scale = identity, NULL center = 0)             */
+  const float* in_shift;
+  const float* in_center;
+  int in_relu;
+} vlnce_regen;
 
 typedef struct {
   /* input transform applied in the A-operand loader BEFORE zero padding:
@@ -124,6 +153,8 @@ typedef struct {
    * launch: 0 or 1 = three bf16 planes (six plane products per multiply), 2 = fp16 planes (three
    * products); must be the `format` the two buffers were made with. */
   int w_format;
+  /* Optional (ABI 148): the launch's input is computed again instead of read; see vlnce_regen. */
+  const vlnce_regen* regen;
 } vlnce_prologue;
 
 /* Train-mode BatchNorm statistics taken BY the convolution (torch.nn.BatchNorm2d.forward in
@@ -158,6 +189,13 @@ typedef struct {
   /* train-mode BatchNorm statistics added by the convolution (see vlnce_bn_sums); excludes
    * stat_partial, scale, shift, residual, act and accumulate.  NULL = off. */
   const vlnce_bn_sums* bn;
+  /* Statistics-only launch (ABI 148): non-zero = the launch takes the statistics of the RAW output
+   * (bn or stat_partial, one of them is required) and stores NO output; y must be NULL.  For a
+   * convolution whose output is cheaper to compute again than to read back: the stride-1 1x1
+   * expansions with Cin = 64 / 128 and Cout % 256 == 0 that conv_s3_kernel covers (w_frag
+   * required).  Any other problem is an error, never another kernel.  The sums are those of the
+   * storing launch up to the order of the atomic adds. */
+  int stats_only;
 } vlnce_epilogue;
 
 long vlnce_conv2d_bn_workspace_bytes(const vlnce_conv_desc* d); /* vlnce_bn_sums.workspace */
@@ -243,7 +281,9 @@ int vlnce_conv2d_last_path(void);
  *                    columns, option "p3_tile"'s numbering), B = VLNCE_CONV_P3_DENSE / _GATHER / _DUAL
  *     P3 / conv_u3:  A = tile rows (64 / 128), B = kind (0 one input, 1 two inputs, 2 two inputs
  *                    each with its own normalisation), C = waves (4 / 8)
- *     P3 / conv_s3:  A = Cin (64 / 128)
+ *     P3 / conv_s3:  A = Cin (64 / 128), B = 1 for the statistics-only instance (ABI 148)
+ *     P3 / conv_r3:  A = channels of the regenerated expansion's input (64 / 128), B = Cout / 32,
+ *                    C = skip kind (1 identity, 2 with its own normalisation)
  *     M3:            A = NT (32-column blocks per wave), B = KSPLIT (waves sharing a reduction),
  *                    C = RB (32-row blocks per workgroup)
  *     X3:            A = tile 1..4 ({128,128} {64,128} {128,64} {64,64}, option "x3_tile"'s
@@ -261,6 +301,7 @@ int vlnce_conv2d_last_path(void);
 #define VLNCE_CONV_KERNEL_P3 0 /* conv_p3_kernel */
 #define VLNCE_CONV_KERNEL_U3 1 /* conv_u3_kernel */
 #define VLNCE_CONV_KERNEL_S3 2 /* conv_s3_kernel */
+#define VLNCE_CONV_KERNEL_R3 3 /* conv_r3_kernel */
 #define VLNCE_CONV_P3_DENSE 0  /* KxK: the patch in LDS            */
 #define VLNCE_CONV_P3_GATHER 1 /* 1x1: rows gathered               */
 #define VLNCE_CONV_P3_DUAL 2   /* 1x1 with the two-input prologue  */

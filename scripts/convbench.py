@@ -3,6 +3,11 @@
 (scale/shift/ReLU) or train-style (raw + BatchNorm partial statistics).
 
     python scripts/convbench.py [--n 64] [--iters 20] [--mode eval|train] [--only substr]
+
+--pair: the block ends of ResNet-50 layers 1-2 as PAIRS of launches, A/B in alternating rounds:
+    old  conv3 (raw output stored) + dual block end (raw output read back)
+    new  statistics-only conv3 + regenerating block end (ops.conv2d_bn_sums stats_only / regen)
+    python scripts/convbench.py --pair --rotate 8 --backlog [--n 64] [--only l1]
 """
 import argparse
 import os
@@ -80,6 +85,82 @@ R18 = [
 ]
 
 
+# name, H(=W), K1 (conv3 input), N2 (next 1x1 output), skip kind, count in the trunk
+PAIRS = [
+    ("l1_end_bn_256_64", 64, 64, 64, "bn", 1),
+    ("l1_end_id_256_64", 64, 64, 64, "identity", 1),
+    ("l1_end_id_256_128", 64, 64, 128, "identity", 1),
+    ("l2_end_bn_512_128", 32, 128, 128, "bn", 1),
+    ("l2_end_id_512_128", 32, 128, 128, "identity", 2),
+    ("l2_end_id_512_256", 32, 128, 256, "identity", 1),
+]
+
+
+def pair_ab(args):
+    dev = "cuda:0"
+    R = args.rotate
+    print(f"# n {args.n}, rotate {R}, iters {args.iters}, rounds {args.rounds} per arm (alternating), "
+          f"{'GPU-paced (backlog)' if args.backlog else 'host-paced'}; us per PAIR of launches")
+    print(f"{'block end':20s} {'M':>8s} {'old min':>9s} {'new min':>9s} {'new/old':>8s}  rounds old | new")
+    tot = [0.0, 0.0]
+    for name, hw, k1, n2, skip, cnt in PAIRS:
+        if args.only and not any(o in name for o in args.only.split(",")):
+            continue
+        n1 = 4 * k1
+        vec = lambda c: (torch.rand(c, device=dev) + 0.5, torch.randn(c, device=dev) * 0.3,   # noqa: E731
+                         torch.randn(c, device=dev) * 0.5)
+        s2, t2, c2 = vec(k1)
+        s3, t3, c3 = vec(n1)
+        sk = vec(n1)
+        w3 = torch.randn(n1, 1, 1, k1, device=dev) * k1 ** -0.5
+        wn = torch.randn(n2, 1, 1, n1, device=dev) * n1 ** -0.5
+        raw2 = [torch.randn(args.n, hw, hw, k1, device=dev) for _ in range(R)]
+        skips = [torch.randn(args.n, hw, hw, n1, device=dev) for _ in range(R)]
+        sides = [torch.empty_like(t) for t in skips]
+        acc3 = torch.zeros((ops.BN_SHARDS, n1, 2), device=dev, dtype=torch.float64)
+        accn = torch.zeros((ops.BN_SHARDS, n2, 2), device=dev, dtype=torch.float64)
+        pro2 = dict(in_scale=s2, in_shift=t2, in_center=c2, in_relu=True)
+        pro3 = dict(in_scale=s3, in_shift=t3, in_center=c3, in_relu=True)
+        if skip == "bn":
+            pro3.update(in2_scale=sk[0], in2_shift=sk[1], in2_center=sk[2])
+        ring = [None] * R   # the old arm's raw3 tensors stay alive R launches: their addresses rotate too
+
+        def old(i):
+            ring[i % R] = ops.conv2d_bn_sums(raw2[i % R], w3, 1, 0, acc3, **pro2)
+            return ops.conv2d_bn_sums(ring[i % R], wn, 1, 0, accn, x2=skips[i % R], side_out=sides[i % R], **pro3)
+
+        def new(i):
+            ops.conv2d_bn_sums(raw2[i % R], w3, 1, 0, acc3, stats_only=True, **pro2)
+            return ops.conv2d_bn_sums(raw2[i % R], wn, 1, 0, accn, x2=skips[i % R], side_out=sides[i % R],
+                                      regen=dict(w=w3, **pro2), **pro3)
+
+        times = ([], [])
+        for arm in (old, new):
+            for i in range(R):
+                arm(i)
+        torch.cuda.synchronize()
+        for _ in range(args.rounds):
+            for a, arm in enumerate((old, new)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                if args.backlog:
+                    torch.cuda._sleep(int(4e7))
+                e0.record()
+                for i in range(args.iters):
+                    arm(i)
+                e1.record()
+                torch.cuda.synchronize()
+                times[a].append(e0.elapsed_time(e1) * 1e3 / args.iters)
+        o, n_ = min(times[0]), min(times[1])
+        fmt = lambda ts: " ".join(f"{t:.1f}" for t in ts)   # noqa: E731
+        print(f"{name:20s} {args.n * hw * hw:8d} {o:9.1f} {n_:9.1f} {n_ / o:8.3f}  {fmt(times[0])} | "
+              f"{fmt(times[1])}  x{cnt}")
+        tot[0] += o * cnt
+        tot[1] += n_ * cnt
+        del raw2, skips, sides, ring
+        torch.cuda.empty_cache()
+    print(f"all block ends per step: old {tot[0] / 1e3:.3f} ms, new {tot[1] / 1e3:.3f} ms")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=64)
@@ -101,10 +182,14 @@ def main():
                     help="R copies of the layer's input (and second input / block output) used in "
                          "rotation: with R x the input bytes beyond the 256 MB Infinity Cache every "
                          "launch reads its operands from HBM, as inside a trunk (the weights stay hot)")
+    ap.add_argument("--pair", action="store_true",
+                    help="A/B of the block ends of ResNet-50 layers 1-2 as pairs of launches (see above)")
     args = ap.parse_args()
     for kv in filter(None, args.opt.split(",")):
         k_, v_ = kv.split("=")
         ops.L().set_option(k_, int(v_))
+    if args.pair:
+        return pair_ab(args)
     dev = "cuda:0"
     tot_t = tot_f = 0.0
     print(f"{'layer':22s} {'M':>8s} {'K':>6s} {'N':>5s} {'us':>9s} {'TF/s':>7s} x cnt")

@@ -8,7 +8,7 @@ import json
 import re
 import sys
 
-CONV = ("conv_p3_kernel", "conv_u3_kernel", "conv_s3_kernel", "conv_x3_kernel", "igemm_kernel",
+CONV = ("conv_p3_kernel", "conv_u3_kernel", "conv_s3_kernel", "conv_r3_kernel", "conv_x3_kernel", "igemm_kernel",
         "stem7_kernel", "conv_m3_kernel")
 
 

@@ -42,13 +42,14 @@ ConvKernel.__doc__ = """family: "f32" | "x3" | "p3" | "m3" (= conv2d_last_path()
 ("conv_p3" | "conv_u3" | "conv_s3", "conv_m3", "conv_x3", "buf" | "splitk" | "v4" | "s" | "stem3" |
 "stem1" | "dual" of igemm_kernel); fmt: plane format 1 / 2 (0: fp32); a, b, c per kernel:
   conv_p3: tile 1..6, mode "dense" | "gather" | "dual", 0      conv_u3: rows, kind 0..2, waves
-  conv_s3: Cin, 0, 0      conv_m3: NT, KSPLIT, RB      conv_x3: tile 1..4, dual 0 / 1, 0
+  conv_s3: Cin, 1 = statistics only, 0      conv_r3: regenerated Cin, Cout / 32, skip kind 1 / 2
+  conv_m3: NT, KSPLIT, RB      conv_x3: tile 1..4, dual 0 / 1, 0
   splitk: the split factor, 0, 0"""
 WgradKernel = collections.namedtuple("WgradKernel", "path tm split")   # path = conv2d_wgrad_last_path()
 
 _FAMILIES = ("f32", "x3", "p3", "m3")
 _KERNELS = {"f32": ("buf", "splitk", "v4", "s", "stem3", "stem1", "dual"), "x3": ("conv_x3",),
-            "p3": ("conv_p3", "conv_u3", "conv_s3"), "m3": ("conv_m3",)}
+            "p3": ("conv_p3", "conv_u3", "conv_s3", "conv_r3"), "m3": ("conv_m3",)}
 _P3_MODES = ("dense", "gather", "dual")
 
 
@@ -86,7 +87,13 @@ class WeightPrepPlan:
 class Prologue(C.Structure):
     _fields_ = [("in_scale", _P), ("in_shift", _P), ("in_center", _P), ("in_relu", _I),
                 ("x2", _P), ("in2_scale", _P), ("in2_shift", _P), ("in2_center", _P),
-                ("side_out", _P), ("w_split", _P), ("w_frag", _P), ("options", _P), ("w_format", _I)]
+                ("side_out", _P), ("w_split", _P), ("w_frag", _P), ("options", _P), ("w_format", _I),
+                ("regen", _P)]
+
+
+class Regen(C.Structure):   # vlnce_regen
+    _fields_ = [("x", _P), ("Cin", _I), ("ldx", _I), ("w_frag", _P), ("in_scale", _P), ("in_shift", _P),
+                ("in_center", _P), ("in_relu", _I)]
 
 
 class Frames(C.Structure):
@@ -105,7 +112,8 @@ class TrajSensor(C.Structure):   # vlnce_traj_sensor
 
 class Epilogue(C.Structure):
     _fields_ = [("scale", _P), ("shift", _P), ("residual", _P), ("ldr", _I), ("act", _I),
-                ("accumulate", _I), ("stat_partial", _P), ("bn", C.POINTER(BnSums))]
+                ("accumulate", _I), ("stat_partial", _P), ("bn", C.POINTER(BnSums)),
+                ("stats_only", _I)]
 
 
 _SIGNATURES = {
@@ -306,7 +314,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 147  # include/vlnce_hip.h
+    ABI = 148  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -325,7 +333,8 @@ class HipLib:
     # ---- dispatch options (vlnce_set_option): the library itself never reads the environment;
     # the VLNCE_* variables of INTEGRATION.md section 8 are translated here, once, at load
     OPTION_NAMES = ("conv_math", "p3", "p3_tile", "s3", "u3", "u3_waves", "x3_tile", "igemm_tile",
-                    "igemm_nobuf", "igemm_no_splitk", "wgrad_tile", "rollout_one_xcd", "m3")
+                    "igemm_nobuf", "igemm_no_splitk", "wgrad_tile", "rollout_one_xcd", "m3", "r3",
+                    "s3_wgs")
 
     def _options_from_env(self):
         for name in self.OPTION_NAMES:
@@ -368,6 +377,14 @@ class HipLib:
                 v = self._conv_math = self.get_option("conv_math")
         return 2 if v == 2 else 1
 
+    def effective_option(self, name):
+        """the value a launch of the calling thread would see: the enclosing `with lib.options(...)`
+        block's, else the process value"""
+        sc = getattr(self._tls, "scoped", None)
+        if sc and sc.get(name, -1) >= 0:
+            return int(sc[name])
+        return self.get_option(name)
+
     def get_option(self, name):
         v = _I(0)
         self._check(self.dll.vlnce_get_option(name.encode(), C.byref(v)), "vlnce_get_option")
@@ -381,7 +398,7 @@ class HipLib:
     # options that choose among the CONVOLUTION kernels travel with each launch
     # (vlnce_prologue.options); the diagnostic switches of the GEMM / rollout entry points, which
     # take no prologue, stay process values
-    PER_LAUNCH = ("conv_math", "p3", "p3_tile", "s3", "u3", "u3_waves", "x3_tile", "m3")
+    PER_LAUNCH = ("conv_math", "p3", "p3_tile", "s3", "u3", "u3_waves", "x3_tile", "m3", "r3", "s3_wgs")
 
     def _launch_options(self, overrides):
         """ctypes int array for vlnce_prologue.options from {name: value} (None = no overrides)"""
@@ -440,27 +457,40 @@ class HipLib:
     def conv2d_fwd(self, x, w, y, g, in_scale=None, in_shift=None, in_relu=0, scale=None,
                    shift=None, residual=None, ldr=0, act=0, accumulate=0, stat_partial=None,
                    in_center=None, x2=None, in2_scale=None, in2_shift=None, in2_center=None,
-                   side_out=None, w_split=None, w_frag=None, bn=None, options=None, w_format=None):
+                   side_out=None, w_split=None, w_frag=None, bn=None, options=None, w_format=None,
+                   stats_only=False, regen=None):
         """bn: train-mode BatchNorm statistics added by the launch (vlnce_bn_sums): (acc
         [16, C, 2] f64, workspace uint8) -- finish them with bn_finalize_sums().
         options: {name: value} dispatch options of this launch (default: those of the enclosing
         `with lib.options(...)` block, else the process values).
         w_format: plane format of w_split / w_frag; default: the format the buffers were made with
-        (ops.split_weights / pack_weights tag them), which any explicit value must agree with."""
+        (ops.split_weights / pack_weights tag them), which any explicit value must agree with.
+        stats_only: the launch takes the statistics (bn or stat_partial) and writes no output; y is
+        None (vlnce_epilogue.stats_only: the short-K 1x1 expansions conv_s3_kernel covers).
+        regen: dict(x, w_frag, in_scale, in_shift, in_center, in_relu) -- the launch's input is the raw
+        output of that stride-1 1x1 expansion of regen["x"], computed again instead of read
+        (vlnce_prologue.regen, conv_r3_kernel); x is None."""
         d = self._desc(g)
-        w_format = _buffer_format(w_format, w_split, w_frag)
+        w_format = _buffer_format(w_format, w_split, w_frag, regen["w_frag"] if regen else None)
+        rg = None
+        if regen is not None:
+            rx = regen["x"]
+            rg = Regen(_ptr(rx), rx.size(-1), rx.size(-1), _ptr(regen["w_frag"]),
+                       _ptr(regen.get("in_scale")), _ptr(regen.get("in_shift")),
+                       _ptr(regen.get("in_center")), int(regen.get("in_relu", 0)))
         opts = self._launch_options(options if options is not None
                                     else getattr(self._tls, "scoped", None))
         pro = Prologue(_ptr(in_scale), _ptr(in_shift), _ptr(in_center), int(in_relu), _ptr(x2),
                        _ptr(in2_scale), _ptr(in2_shift), _ptr(in2_center), _ptr(side_out),
                        _ptr(w_split), _ptr(w_frag),
-                       C.cast(opts, C.c_void_p) if opts is not None else None, int(w_format))
+                       C.cast(opts, C.c_void_p) if opts is not None else None, int(w_format),
+                       C.cast(C.pointer(rg), C.c_void_p) if rg is not None else None)
         bnp = None
         if bn is not None:
             acc, ws = bn
             bnp = C.pointer(BnSums(_ptr(acc), _ptr(ws), ws.numel() * ws.element_size()))
         epi = Epilogue(_ptr(scale), _ptr(shift), _ptr(residual), int(ldr), int(act),
-                       int(accumulate), _ptr(stat_partial), bnp)
+                       int(accumulate), _ptr(stat_partial), bnp, int(bool(stats_only)))
         self._check(self.dll.vlnce_conv2d_fwd(_ptr(x), _ptr(w), _ptr(y), C.byref(d), C.byref(pro),
                                               C.byref(epi), _stream()), "vlnce_conv2d_fwd")
 

@@ -39,7 +39,9 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // 146: vlnce_conv2d_last_kernel / vlnce_conv2d_wgrad_last_kernel (which kernel INSTANCE the thread's last
 // launch ran on: family, plane format, tile / mode / template arguments; VLNCE_CONV_KERNEL_*).
 // 147: vlnce_traj_append / vlnce_traj_sensor, vlnce_dagger_mix_actions (DAgger rollout collection on the device).
-extern "C" int vlnce_version(void) { return 147; }
+// 148: vlnce_epilogue.stats_only (a convolution that takes its BatchNorm statistics and stores no output),
+// vlnce_prologue.regen (a block end that computes conv3's output again instead of reading it), options "r3", "s3_wgs".
+extern "C" int vlnce_version(void) { return 148; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)
@@ -52,10 +54,10 @@ const OptDef kOpts[VLNCE_OPT_COUNT] = {
     {"conv_math", 2},   {"p3", 2},          {"p3_tile", 0},         {"s3", 1},
     {"u3", 1},          {"u3_waves", 8},    {"x3_tile", 0},         {"igemm_tile", 0},
     {"igemm_nobuf", 0}, {"igemm_no_splitk", 0}, {"wgrad_tile", 64}, {"rollout_one_xcd", 0},
-    {"m3", 1},
+    {"m3", 1},          {"r3", 1},          {"s3_wgs", 0},
 };
 std::atomic<int> g_opt[VLNCE_OPT_COUNT] = {
-    {2}, {2}, {0}, {1}, {1}, {8}, {0}, {0}, {0}, {0}, {64}, {0}, {1},
+    {2}, {2}, {0}, {1}, {1}, {8}, {0}, {0}, {0}, {0}, {64}, {0}, {1}, {1}, {0},
 };
 int opt_index(const char* name) {
   if (name)

@@ -24,6 +24,12 @@
 // 8 waves (two per SIMD), wave w owns columns [32w, 32w + 32) of a 64 x 256 tile; one barrier
 // per tile.  Arithmetic, patch rows, fragment layout and statistics are conv_u3_kernel's
 // (conv_u3.hip).
+// STORE = false is the statistics-only launch (vlnce_epilogue.stats_only): the same tiles, the same
+// MFMA order and the same wave_bn_tile / wave_stats_block calls on the same accumulators, but no
+// output: the stores(...) lambda, the second accumulator set and the store interleave are
+// compiled out, and a tile's statistics are taken right behind its own MFMAs.  It is the first
+// half of a block end that regenerates conv3's output instead of reading it back (DESIGN.md
+// section 6): the BatchNorm statistics need a pass over conv3's INPUT, not a stored output.
 #include "igemm_shared.h"
 
 using namespace vlnce_detail;
@@ -31,7 +37,7 @@ using namespace vlnce_detail;
 namespace vlnce_detail {
 namespace {
 
-template <int NCC, int MATH>
+template <int NCC, int MATH, bool STORE>
 __global__ __launch_bounds__(512) void conv_s3_kernel(IgemmParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef Planes<MATH> PL;
@@ -59,8 +65,9 @@ __global__ __launch_bounds__(512) void conv_s3_kernel(IgemmParams p) {
   const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(reinterpret_cast<const char*>(p.Bfrag)), 0, (int)((long)p.N * p.K * 6),
       0x00020000);
+  // (STORE = false: C is null and c_bytes 0 -- the descriptor is never used)
   const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<char*>(p.C), 0, (int)p.c_bytes, 0x00020000);
+      reinterpret_cast<char*>(p.C), 0, STORE ? (int)p.c_bytes : 0, 0x00020000);
   const float relu_floor = p.in_relu ? 0.f : -__builtin_huge_valf();
   const bool relu_out = p.act == VLNCE_ACT_RELU;  // the launcher admits VLNCE_ACT_NONE / _RELU only
 
@@ -110,9 +117,11 @@ __global__ __launch_bounds__(512) void conv_s3_kernel(IgemmParams p) {
   };
 #pragma unroll
   for (int k = 0; k < RING; ++k) load_raw(raw[k], k);
-  f32x16 acc[2][MT];  // [tile parity][row block]
+  constexpr int NACC = STORE ? 2 : 1;
+  constexpr int B1 = NACC - 1;   // the accumulator set of the odd tiles
+  f32x16 acc[NACC][MT];  // [tile parity][row block]
 #pragma unroll
-  for (int b = 0; b < 2; ++b)
+  for (int b = 0; b < NACC; ++b)
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -173,7 +182,8 @@ __global__ __launch_bounds__(512) void conv_s3_kernel(IgemmParams p) {
     load_raw(r, round + RING);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (has_prev) stats(prv, m0_prev);
+    if constexpr (STORE)
+      if (has_prev) stats(prv, m0_prev);
 #pragma unroll
     for (int c = 0; c < NCC; ++c)
 #pragma unroll
@@ -192,41 +202,50 @@ __global__ __launch_bounds__(512) void conv_s3_kernel(IgemmParams p) {
             cur[i] = plane_mfma<MATH>(f[i][PL::PA[q]], bres[c * 2 + s2][PL::PB[q]], cur[i]);
         // the previous tile's next SPS stores ride behind this slab's 12 MFMAs (a tile whose
         // predecessor does not exist stores to the out-of-range offset: no branch in the body)
-        stores(prv, has_prev ? m0_prev : p.M, (c * 2 + s2) * SPS, SPS);
-        // schedule of the slab: its 12 MFMAs with the SPS stores spread evenly between them
-        // (K = 64: 2 MFMAs, store, 1 MFMA, store, four times; K = 128: 3 MFMAs, store, four times)
-        if constexpr (MATH == MATH_F16X3) {
-          // 6 MFMAs per slab: K = 64: MFMA, store, store, MFMA, store (x2, then 2 MFMAs + 2 stores);
-          // K = 128: 3 MFMAs, 2 stores, twice
+        if constexpr (STORE) {
+          stores(prv, has_prev ? m0_prev : p.M, (c * 2 + s2) * SPS, SPS);
+          // schedule of the slab: its 12 MFMAs with the SPS stores spread evenly between them
+          // (K = 64: 2 MFMAs, store, 1 MFMA, store, four times; K = 128: 3 MFMAs, store, four times)
+          if constexpr (MATH == MATH_F16X3) {
+            // 6 MFMAs per slab: K = 64: MFMA, store, store, MFMA, store (x2, then 2 MFMAs + 2 stores);
+            // K = 128: 3 MFMAs, 2 stores, twice
 #pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            if constexpr (SPS == 8) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-            } else {
-              __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
+            for (int g = 0; g < 2; ++g) {
+              if constexpr (SPS == 8) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
+              } else {
+                __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+                __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
+              }
             }
-          }
-        } else {
+          } else {
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            if constexpr (SPS == 8) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);  // VMEM write
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-            } else {
-              __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-              __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
+            for (int g = 0; g < 4; ++g) {
+              if constexpr (SPS == 8) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA
+                __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);  // VMEM write
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
+              } else {
+                __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+                __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
+              }
             }
           }
         }
       }
+    if constexpr (!STORE) {   // nothing to hide the statistics under: taken here, registers cleared behind
+      stats(cur, m0);
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int r2 = 0; r2 < 16; ++r2) cur[i][r2] = 0.f;
+    }
   };
   // The first two tiles are peeled: the compiler's s_waitcnt at a loop header is the minimum
   // over the paths into it, and entered straight from the preamble the first wait for raw rows
@@ -234,19 +253,20 @@ __global__ __launch_bounds__(512) void conv_s3_kernel(IgemmParams p) {
   // second tile (round 3's unpeeled form had exactly that: vmcnt(3) / vmcnt(35) alternated in its ISA).
   // Behind the peeled tiles both ways into the loop have a tile's 32 stores after the request.
   if (my_tiles <= 0) return;  // (cannot happen with launch_s3's grid; uniform per workgroup)
-  tile(0, raw[0], acc[0], acc[1]);
-  if (1 < my_tiles) tile(1, raw[RING - 1], acc[1], acc[0]);
+  tile(0, raw[0], acc[0], acc[B1]);
+  if (1 < my_tiles) tile(1, raw[RING - 1], acc[B1], acc[0]);
   for (int round = 2; round < my_tiles; round += 2) {
-    tile(round, raw[0], acc[0], acc[1]);
-    if (round + 1 < my_tiles) tile(round + 1, raw[RING - 1], acc[1], acc[0]);
+    tile(round, raw[0], acc[0], acc[B1]);
+    if (round + 1 < my_tiles) tile(round + 1, raw[RING - 1], acc[B1], acc[0]);
   }
-  // the last tile's epilogue has nothing left to hide under
-  {
+  if constexpr (!STORE) {
+    if (p.bn.acc != nullptr) wave_bn_flush(wbn, p.bn.acc, p.N, half, l31);
+  } else {  // the last tile's epilogue has nothing left to hide under
     const int m0 = (wg + (my_tiles - 1) * nwg) * BM;
     if ((my_tiles - 1) & 1) {
-      stats(acc[1], m0);
+      stats(acc[B1], m0);
       if (p.bn.acc != nullptr) wave_bn_flush(wbn, p.bn.acc, p.N, half, l31);  // in front of the stores
-      stores(acc[1], m0, 0, 32);
+      stores(acc[B1], m0, 0, 32);
     } else {
       stats(acc[0], m0);
       if (p.bn.acc != nullptr) wave_bn_flush(wbn, p.bn.acc, p.N, half, l31);
@@ -256,10 +276,10 @@ __global__ __launch_bounds__(512) void conv_s3_kernel(IgemmParams p) {
 #endif
 }
 
-template <int NCC, int MATH>
+template <int NCC, int MATH, bool STORE>
 int launch_s3(const IgemmParams& p, hipStream_t stream) {
   constexpr int smem_bytes = 2 * NCC * 64 * Planes<MATH>::ROW + 3 * NCC * 32 * 4;  // two tile patches + the prologue vectors
-  auto kern = conv_s3_kernel<NCC, MATH>;
+  auto kern = conv_s3_kernel<NCC, MATH, STORE>;
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -277,18 +297,38 @@ int launch_s3(const IgemmParams& p, hipStream_t stream) {
   const int cus = x3_cus();
   long grid = (long)q.tiles_m * q.tiles_n;
   if (grid > cus) grid = cus - cus % q.tiles_n;  // resident workgroups, a multiple of tiles_n
+  if (const int cap = vlnce_opt(VLNCE_OPT_S3_WGS); cap > 0 && grid > cap)   // option "s3_wgs" (tests)
+    grid = cap >= q.tiles_n ? cap - cap % q.tiles_n : q.tiles_n;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem_bytes, stream, q);
   VLNCE_CHECK_LAUNCH("conv_s3");
   return 0;
 }
 
+template <bool STORE>
+int s3_launch_(const IgemmParams& p, hipStream_t stream) {
+  if (p.math == MATH_F16X3)
+    return p.Cin == 64 ? launch_s3<2, MATH_F16X3, STORE>(p, stream)
+                       : launch_s3<4, MATH_F16X3, STORE>(p, stream);
+  return p.Cin == 64 ? launch_s3<2, MATH_BF16X6, STORE>(p, stream)
+                     : launch_s3<4, MATH_BF16X6, STORE>(p, stream);
+}
+
 }  // namespace
 
 int s3_launch(const IgemmParams& p, hipStream_t stream) {   // Cin is 64 or 128 (the router's test)
-  note_conv_kernel(VLNCE_CONV_KERNEL(VLNCE_CONV_PATH_P3, p.math, VLNCE_CONV_KERNEL_S3, p.Cin == 64 ? 64 : 128, 0, 0));
-  if (p.math == MATH_F16X3)
-    return p.Cin == 64 ? launch_s3<2, MATH_F16X3>(p, stream) : launch_s3<4, MATH_F16X3>(p, stream);
-  return p.Cin == 64 ? launch_s3<2, MATH_BF16X6>(p, stream) : launch_s3<4, MATH_BF16X6>(p, stream);
+  // the statistics-only instance has no output: a launch must say which one it means
+  if (p.stats_only ? p.C != nullptr : p.C == nullptr) {
+    vlnce_set_error("conv_s3: %s", p.stats_only ? "a statistics-only launch takes no output pointer"
+                                                : "null output");
+    return 1;
+  }
+  if (p.stats_only && p.bn.acc == nullptr && p.stat_partial == nullptr) {
+    vlnce_set_error("conv_s3: a statistics-only launch needs bn or stat_partial");
+    return 1;
+  }
+  note_conv_kernel(VLNCE_CONV_KERNEL(VLNCE_CONV_PATH_P3, p.math, VLNCE_CONV_KERNEL_S3,
+                                     p.Cin == 64 ? 64 : 128, p.stats_only ? 1 : 0, 0));
+  return p.stats_only ? s3_launch_<false>(p, stream) : s3_launch_<true>(p, stream);
 }
 
 }  // namespace vlnce_detail

@@ -1283,6 +1283,7 @@ void fill_epilogue(IgemmParams& p, const vlnce_epilogue* e) {
   p.stat_partial = e ? e->stat_partial : nullptr;
   p.bn = vlnce_bn_sums{};
   if (e && e->bn) p.bn = *e->bn;
+  p.stats_only = e ? e->stats_only : 0;
 }
 
 bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
@@ -1510,7 +1511,13 @@ static void note_f32_kernel(int kernel, int a = 0) {
 extern "C" int vlnce_conv2d_fwd(const float* x, const float* w, float* y, const vlnce_conv_desc* d,
                                 const vlnce_prologue* pro, const vlnce_epilogue* epi,
                                 vlnce_stream_t stream) {
-  VLNCE_CHECK_ARG(x && w && y && d, "conv2d_fwd: null argument");
+  const vlnce_regen* const regen = pro ? pro->regen : nullptr;
+  VLNCE_CHECK_ARG((regen ? x == nullptr : x != nullptr) && w && d,
+                  "conv2d_fwd: %s", regen ? "a launch that regenerates its input takes no x" : "null argument");
+  const bool stats_only = epi && epi->stats_only;
+  VLNCE_CHECK_ARG(stats_only ? y == nullptr : y != nullptr,
+                  "conv2d_fwd: %s", stats_only ? "a statistics-only launch takes no output (y must be NULL)"
+                                               : "null argument");
   VLNCE_CHECK_ARG(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0,
                   "conv2d_fwd: bad shape");
   const VlnceOptScope opt_scope(pro ? pro->options : nullptr);   // this launch's dispatch options
@@ -1595,10 +1602,56 @@ extern "C" int vlnce_conv2d_fwd(const float* x, const float* w, float* y, const 
   p.splitk = 1;
   p.a_bytes = (((long)d->N * d->H * d->W - 1) * p.lda + d->Cin) * 4;
   p.b_bytes = (long)d->Cout * p.K * 4;
-  p.c_bytes = ((M - 1) * p.ldc + d->Cout) * 4;
+  p.c_bytes = stats_only ? 0 : ((M - 1) * p.ldc + d->Cout) * 4;
   p.stat_rows = stat_rows_for(d);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   g_last_path = VLNCE_CONV_PATH_F32;
+  if (regen != nullptr) {
+    // one kernel does this (conv_r3_kernel); what it does not cover is an error
+    VLNCE_CHECK_ARG(!stats_only && conv_math() && p.Bfrag && regen->w_frag && regen->x && d->KH == 1 &&
+                        d->KW == 1 && d->stride == 1 && d->pad == 0 && d->Cin == 4 * regen->Cin &&
+                        (regen->Cin == 64 || regen->Cin == 128) && regen->ldx >= regen->Cin &&
+                        regen->ldx % 4 == 0 && p.lda % 4 == 0 && p.A2 && p.side_out && p.in_scale &&
+                        !p.scale && !p.shift && !p.residual && !p.act && !p.accumulate &&
+                        (p.stat_partial == nullptr || p.stat_rows == 32) &&
+                        ((p.in2_scale == nullptr) == (p.in2_shift == nullptr)) &&
+                        (!p.in2_center || p.in2_scale) &&
+                        ((regen->in_scale == nullptr) == (regen->in_shift == nullptr)) &&
+                        (!regen->in_center || regen->in_scale),
+                    "conv2d_fwd: regen needs a stride-1 1x1 launch with Cin = 4 x regen.Cin (64 / 128), "
+                    "w_frag of both convolutions, x2, side_out, in_scale / in_shift and a raw output");
+    RegenParams g{};
+    g.x = regen->x;
+    g.w_frag = regen->w_frag;
+    g.scale = regen->in_scale;
+    g.shift = regen->in_shift;
+    g.center = regen->in_center;
+    g.relu = regen->in_relu;
+    g.K1 = regen->Cin;
+    g.ldx = regen->ldx;
+    g.x_bytes = ((M - 1) * regen->ldx + regen->Cin) * 4;
+    VLNCE_CHECK_ARG(aligned16(g.x) && aligned16(p.A2) && aligned16(p.side_out) && aligned16(y) &&
+                        (!g.scale || (aligned16(g.scale) && aligned16(g.shift))) &&
+                        (!g.center || aligned16(g.center)) && g.x_bytes < 0x7fffffffL &&
+                        p.a_bytes < 0x7fffffffL && p.c_bytes < 0x7fffffffL,
+                    "conv2d_fwd: regen needs 16-byte aligned operands below 2 GiB");
+    g_last_path = VLNCE_CONV_PATH_P3;
+    return r3_launch(p, g, s);
+  }
+  if (stats_only) {
+    // one kernel has this mode (conv_s3_kernel<.., STORE = false>); what it does not cover is an error
+    VLNCE_CHECK_ARG(p.bn.acc != nullptr || p.stat_partial != nullptr,
+                    "conv2d_fwd: a statistics-only launch needs bn or stat_partial");
+    VLNCE_CHECK_ARG(conv_math() && p.Bfrag && v4 && buf_ok(p) && d->KH == 1 && d->KW == 1 &&
+                        d->stride == 1 && d->pad == 0 && (d->Cin == 64 || d->Cin == 128) &&
+                        d->Cout % 256 == 0 && d->Cout / 256 <= 8 && !p.A2 && !p.side_out &&
+                        !p.scale && !p.shift && !p.residual && !p.act && !p.accumulate &&
+                        (p.stat_partial == nullptr || p.stat_rows == 32),
+                    "conv2d_fwd: no statistics-only kernel for this problem (stride-1 1x1, Cin 64 / 128, "
+                    "Cout %% 256 == 0, w_frag, a plain prologue, no epilogue arithmetic)");
+    g_last_path = VLNCE_CONV_PATH_P3;
+    return s3_launch(p, s);
+  }
   if (p.A2 != nullptr || p.side_out != nullptr) {
     VLNCE_CHECK_ARG(p.A2 && p.in_scale && d->KH == 1 && d->KW == 1 && d->stride == 1 &&
                         d->pad == 0 && v4 && buf_ok(p) && aligned16(p.A2) &&

@@ -59,7 +59,21 @@ struct IgemmParams {
   int tiles_m, tiles_n;
   int splitk;  // > 1: blockIdx.y owns a K range and atomically adds into a pre-zeroed C
   int stat_rows;  // rows per statistics partial (vlnce_conv2d_tile_rows)
+  int stats_only; // conv_s3_kernel: take the statistics, store nothing (C is null)
   long a_bytes, b_bytes, c_bytes;  // extents of A / B / C for the buffer descriptors
+};
+
+// vlnce_prologue.regen as conv_r3_kernel takes it: the 1x1 expansion whose output the launch's
+// input would have been (conv_r3.hip)
+struct RegenParams {
+  const float* x;       // [M, K1] raw input of that expansion, row stride ldx
+  const void* w_frag;   // its weights as B fragments (format IgemmParams::math)
+  const float* scale;   // its operand prologue: (x - center) * scale + shift, ReLU
+  const float* shift;
+  const float* center;
+  int relu;
+  int K1, ldx;
+  long x_bytes;
 };
 
 __device__ __forceinline__ f32x4 ldg4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
@@ -469,6 +483,7 @@ int p3_try_launch(const IgemmParams& p, hipStream_t stream);
 constexpr int U3_MAX_CIN = 4096;   // conv_u3_kernel: input channels whose prologue vectors fit its LDS
 int u3_launch(const IgemmParams& p, int bm, int dual_kind, int waves, hipStream_t stream);
 int s3_launch(const IgemmParams& p, hipStream_t stream);   // conv_s3.hip: Cin = 64 or 128
+int r3_launch(const IgemmParams& p, const RegenParams& g, hipStream_t stream);   // conv_r3.hip
 int m3_try_launch(const IgemmParams& p, hipStream_t stream);   // conv_m3.hip
 // wgrad_x6.hip: the weight gradient on the 16-bit pipe (three bf16 planes); -1 = not covered
 int wgrad_x6_try_launch(const float* x, const float* dy, float* dw, const vlnce_conv_desc* d,

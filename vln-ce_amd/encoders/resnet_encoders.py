@@ -17,7 +17,7 @@ ops get channels-last rows without a copy.
 """
 import os
 import warnings
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -284,6 +284,11 @@ class Bottleneck(nn.Module):
         return [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
 
 
+# conv3's output as a recipe instead of a tensor (HipResNetTrunk._regen_next): x = conv2's raw
+# output, w = conv3's packed OHWI weights, pend = bn2's pending normalisation
+_Regen = namedtuple("_Regen", "x w pend", defaults=(None,))
+
+
 class _GlobalAvgPool(nn.Module):
     out_hw = (1, 1)
 
@@ -335,10 +340,10 @@ class HipResNetTrunk(DropsGraphsOnApply, nn.Sequential):
     # normalisation (+ReLU) is then applied by whoever consumes the raw tensor: the next
     # conv's operand loader, the max-pool, or the block-end add pass.
     def _conv_stats(self, x, conv, bn, touched, prologue=None, in_relu=False, s2d=False,
-                    dual=None):
-        pro = {}
+                    dual=None, **extra):
+        pro = dict(extra)   # stats_only / regen of the regenerating block end (ops.conv2d_bn_sums)
         if prologue is not None:
-            pro = dict(in_scale=prologue[0], in_shift=prologue[1], in_relu=in_relu,
+            pro.update(in_scale=prologue[0], in_shift=prologue[1], in_relu=in_relu,
                        in_center=prologue[2] if len(prologue) > 2 else None)
         if dual is not None:  # (x2, pending norm of x2 | None, side_out)
             x2, p2, side = dual
@@ -349,6 +354,7 @@ class HipResNetTrunk(DropsGraphsOnApply, nn.Sequential):
                           (self._cache.conv(conv), conv.stride[0], conv.padding[0]))
         assert bn.momentum is not None
         if os.environ.get("VLNCE_BN_FUSED", "1") == "0":   # A/B: tile moments + finalize launch(es)
+            assert not extra
             y, stats = ops.conv2d_nhwc(x, w, stride, pad, want_stats=True, **pro)
             pend = ops.bn_finalize(stats, y.numel() // y.size(-1), bn.weight, bn.bias, bn.eps,
                                    bn.momentum, bn.running_mean, bn.running_var)
@@ -375,25 +381,75 @@ class HipResNetTrunk(DropsGraphsOnApply, nn.Sequential):
                                    act=ops.ACT_RELU, out=raw)
 
     @staticmethod
-    def _takes_pending(blk, pending):
+    def _takes_pending(blk, numel):
+        """numel: elements of the block's (pending) input"""
         conv = blk.stages()[0][0]
         return (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
-                and conv.in_channels % 32 == 0 and pending[0].numel() * 4 < (1 << 31)
+                and conv.in_channels % 32 == 0 and numel * 4 < (1 << 31)
                 and os.environ.get("VLNCE_FUSE_BLOCK_END", "1") != "0")
 
-    def _block_train(self, x, pending, blk, touched):
-        """x: materialised block input or None when `pending` holds it; returns the new pending."""
+    # Layers 1-2, option "r3": conv3's raw output is not stored at all.  conv3 runs as a
+    # statistics-only launch (bn3's batch statistics need a pass over conv3's INPUT, a quarter of the
+    # bytes), and the block end inside the next block's first 1x1 computes conv3's tile again in
+    # registers (ops._regen_launch, conv_r3_kernel): `pending` then carries a _Regen recipe in
+    # place of raw3.  Only this no-grad path: the recorded path needs raw3 for backward.
+    # (K1, Cout of the next 1x1) taken under "r3" = 1: the shapes on which the pair was measured
+    # faster from HBM than conv_s3 + the dual block end (profiles/block_end_regen_pair_ab.txt: all
+    # six block-end shapes of layers 1-2 at num_envs 64, 0.88-0.97 of the old pair's time)
+    _R3_MEASURED_FASTER = frozenset({(64, 64), (64, 128), (128, 128), (128, 256)})
+
+    def _regen_next(self, blk, nxt, raw2):
+        """the _Regen recipe if this block's conv3 may leave its output unstored, else None"""
+        mode = ops.regen_mode()
+        if mode <= 0 or nxt is None or not isinstance(blk, Bottleneck):
+            return None
+        conv3, c1 = blk.conv3, nxt.stages()[0][0]
+        k1, n2 = conv3.in_channels, c1.out_channels
+        if (conv3.kernel_size != (1, 1) or conv3.stride != (1, 1) or conv3.padding != (0, 0)
+                or k1 not in (64, 128) or conv3.out_channels != 4 * k1
+                or c1.in_channels != 4 * k1 or n2 not in ((64, 128) if k1 == 64 else (128, 256))
+                or os.environ.get("VLNCE_BN_FUSED", "1") == "0"
+                or not self._takes_pending(nxt, raw2.numel() * 4)):
+            return None
+        # "r3" = 1: where it was measured -- these shapes at launches that give every CU at least four
+        # 64-row tiles (conv_s3_kernel's own rule; num_envs 64: 4 096 / 1 024 tiles); smaller launches
+        # stay on the kernels tuned for them
+        rows = raw2.numel() // k1
+        cus = torch.cuda.get_device_properties(raw2.device).multi_processor_count // 8 * 8
+        if mode == 1 and ((k1, n2) not in self._R3_MEASURED_FASTER or rows < 64 * 4 * cus):
+            return None
+        w3, w1 = self._cache.conv(conv3), self._cache.conv(c1)
+        if ops.plane_format(None, w3) != ops.plane_format(None, w1):   # (one of them pinned to format 1)
+            return None
+        return _Regen(raw2, w3)
+
+    def _block_train(self, x, pending, blk, touched, nxt=None):
+        """x: materialised block input or None when `pending` holds it; nxt: the block behind this
+        one (None: the trunk's last); returns the new pending."""
         st = blk.stages()
-        if pending is not None and self._takes_pending(blk, pending):
+        if pending is not None and self._takes_pending(blk, pending[2].numel()):
             raw3, pend3, skip, pskip = pending
-            x = torch.empty_like(raw3)
-            raw, pend = self._conv_stats(raw3, st[0][0], st[0][1], touched, prologue=pend3,
-                                         in_relu=True, dual=(skip, pskip, x))
+            x = torch.empty_like(skip)
+            if isinstance(raw3, _Regen):   # (raw2, W3, bn2's pending normalisation)
+                raw, pend = self._conv_stats(
+                    raw3.x, st[0][0], st[0][1], touched, prologue=pend3, in_relu=True, dual=(skip, pskip, x),
+                    regen=dict(w=raw3.w, in_scale=raw3.pend[0], in_shift=raw3.pend[1], in_center=raw3.pend[2],
+                               in_relu=True))
+            else:
+                raw, pend = self._conv_stats(raw3, st[0][0], st[0][1], touched, prologue=pend3,
+                                             in_relu=True, dual=(skip, pskip, x))
         else:
             if pending is not None:
                 x = self._materialise(pending)
             raw, pend = self._conv_stats(x, st[0][0], st[0][1], touched)
-        for conv, bn in st[1:]:
+        for conv, bn in st[1:-1]:
+            raw, pend = self._conv_stats(raw, conv, bn, touched, prologue=pend, in_relu=True)
+        conv, bn = st[-1]
+        rg = self._regen_next(blk, nxt, raw)
+        if rg is not None:
+            _, pend3 = self._conv_stats(raw, conv, bn, touched, prologue=pend, in_relu=True, stats_only=True)
+            raw, pend = rg._replace(pend=pend), pend3
+        else:
             raw, pend = self._conv_stats(raw, conv, bn, touched, prologue=pend, in_relu=True)
         if blk.downsample is not None:
             rd, pd = self._conv_stats(x, blk.downsample[0], blk.downsample[1], touched)
@@ -430,7 +486,8 @@ class HipResNetTrunk(DropsGraphsOnApply, nn.Sequential):
             raise NotImplementedError("mixed train/eval BatchNorm modes inside one trunk")
         key = (signature, modes[0], tuple(p._version for p in self._plist(checked=False)),
                id(self.input_scale[0]), len(self._modules),
-               0 if modes[0] else self._bn_gen, ops.plane_format())
+               0 if modes[0] else self._bn_gen, ops.plane_format(),
+               ops.regen_mode() if modes[0] else 0)
         return key, modes[0]
 
     def graph_ready(self, x):
@@ -477,13 +534,13 @@ class HipResNetTrunk(DropsGraphsOnApply, nn.Sequential):
                     x = self._conv_bn_eval(x, kids[0], kids[1], True, prologue=pro, s2d=s2d)
                     x = ops.maxpool3x3s2(x)
             pending = None
-            for stage in kids[4:8]:
-                for blk in stage:
-                    if train:
-                        pending = self._block_train(x, pending, blk, touched)
-                        x = None
-                    else:
-                        x = self._block_eval(x, blk)
+            blocks = [blk for stage in kids[4:8] for blk in stage]
+            for blk, nxt in zip(blocks, blocks[1:] + [None]):
+                if train:
+                    pending = self._block_train(x, pending, blk, touched, nxt)
+                    x = None
+                else:
+                    x = self._block_eval(x, blk)
             if pending is not None:
                 x = self._materialise(pending)
             for pool in kids[8:]:

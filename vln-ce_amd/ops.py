@@ -139,17 +139,43 @@ def conv_geometry(x, w, stride, pad, ldx=None):
                 Ho=Ho, Wo=Wo, ldx=ldx or Cin, ldy=Cout)
 
 
+def _regen_launch(x, regen, x2, fmt):
+    """(x for the library, vlnce_regen fields) of a launch whose input is REGENERATED: `x` is the
+    raw input of the stride-1 1x1 expansion regen["w"] (its prologue: regen["in_scale"] / ["in_shift"] /
+    ["in_center"] / ["in_relu"]), and the launch computes that expansion's raw output again instead of
+    reading it (vlnce_prologue.regen).  x2 (the skip) has the shape the launch's input would have."""
+    w3 = regen["w"]
+    assert x2 is not None and x.is_contiguous() and w3.is_contiguous()
+    assert x.shape[:3] == x2.shape[:3] and w3.shape[0] == x2.shape[3] and w3.shape[3] == x.shape[3]
+    frag = pack_weights(w3, fmt)
+    if frag is None:
+        raise RuntimeError("regen: the regenerated convolution has no fragment image")
+    return None, dict(x=x, w_frag=frag, in_scale=regen.get("in_scale"), in_shift=regen.get("in_shift"),
+                      in_center=regen.get("in_center"), in_relu=int(regen.get("in_relu", 0)))
+
+
+def regen_mode():
+    """option "r3" as the calling thread's next launch sees it: which block ends of ResNet-50 layers
+    1-2 leave conv3's output unstored (0 none, 1 the measured shapes, 2 all).  0 with the fp32-MFMA
+    arithmetic (the two kernels are plane kernels) and with a library object without dispatch options."""
+    lib = L()
+    if not hasattr(lib, "effective_option") or not lib.effective_option("conv_math"):
+        return 0
+    return lib.effective_option("r3")
+
+
 def conv2d_nhwc(x, w_ohwi, stride, pad, *, in_scale=None, in_shift=None, in_center=None,
                 in_relu=False, scale=None, shift=None, residual=None, act=ACT_NONE,
                 want_stats=False, x2=None, in2_scale=None, in2_shift=None, in2_center=None,
-                side_out=None, w_format=None):
+                side_out=None, w_format=None, regen=None):
     """y[N,Ho,Wo,Cout] = act((conv(prologue(x), w)) * scale + shift + residual), with
     prologue(x) = act((x - in_center) * in_scale + in_shift).
     want_stats=True additionally returns the BatchNorm partials of the RAW
     accumulator: (partial[tiles_m, Cout, 2], tiles_m, tile_rows).
-    w_format: plane format of the launch (plane_format()); backward launches pass PLANES_BF16X6."""
+    w_format: plane format of the launch (plane_format()); backward launches pass PLANES_BF16X6.
+    regen: see _regen_launch -- x is then the regenerated expansion's raw input."""
     assert x.is_contiguous() and w_ohwi.is_contiguous()
-    g = conv_geometry(x, w_ohwi, stride, pad)
+    g = conv_geometry(x if regen is None else x2, w_ohwi, stride, pad)
     y = torch.empty((g["N"], g["Ho"], g["Wo"], g["Cout"]), device=x.device, dtype=torch.float32)
     stats = None
     partial = None
@@ -161,15 +187,18 @@ def conv2d_nhwc(x, w_ohwi, stride, pad, *, in_scale=None, in_shift=None, in_cent
         assert residual.is_contiguous() and residual.shape == y.shape
     dual = {}
     if x2 is not None:  # dual-input prologue (+ materialised transformed input), see the header
-        assert x2.is_contiguous() and x2.shape == x.shape
-        assert side_out is None or (side_out.is_contiguous() and side_out.shape == x.shape)
+        assert x2.is_contiguous() and (regen is not None or x2.shape == x.shape)
+        assert side_out is None or (side_out.is_contiguous() and side_out.shape == x2.shape)
         dual = dict(x2=x2, in2_scale=in2_scale, in2_shift=in2_shift, in2_center=in2_center,
                     side_out=side_out)
     fmt = plane_format(w_format, w_ohwi)
+    more = {}
+    if regen is not None:
+        x, more["regen"] = _regen_launch(x, regen, x2, fmt)
     L().conv2d_fwd(x, w_ohwi, y, g, in_scale=in_scale, in_shift=in_shift, in_center=in_center,
                    in_relu=int(in_relu), **dual, scale=scale, shift=shift, residual=residual, ldr=g["Cout"], act=act,
                    stat_partial=partial, w_split=split_weights(w_ohwi, fmt),
-                   w_frag=pack_weights(w_ohwi, fmt), w_format=fmt)
+                   w_frag=pack_weights(w_ohwi, fmt), w_format=fmt, **more)
     return (y, stats) if want_stats else y
 
 
@@ -189,21 +218,29 @@ def _bn_state(bn):
     return acc
 
 
-def conv2d_bn_sums(x, w_ohwi, stride, pad, acc, **pro):
+def conv2d_bn_sums(x, w_ohwi, stride, pad, acc, stats_only=False, **pro):
     """raw convolution output; the launch adds the output's per-channel {sum, sum of squares} to
-    `acc` (vlnce_bn_sums).  `pro`: the operand-loader arguments of conv2d_nhwc."""
+    `acc` (vlnce_bn_sums).  `pro`: the operand-loader arguments of conv2d_nhwc (`regen` included).
+    stats_only=True: the launch adds the sums and stores nothing (vlnce_epilogue.stats_only; the
+    short-K 1x1 expansions only, anything else raises); returns an EMPTY [N,Ho,Wo,0] tensor."""
     assert x.is_contiguous() and w_ohwi.is_contiguous()
-    g = conv_geometry(x, w_ohwi, stride, pad)
-    y = torch.empty((g["N"], g["Ho"], g["Wo"], g["Cout"]), device=x.device, dtype=torch.float32)
+    regen = pro.pop("regen", None)
+    g = conv_geometry(x if regen is None else pro.get("x2"), w_ohwi, stride, pad)
+    y = torch.empty((g["N"], g["Ho"], g["Wo"], 0 if stats_only else g["Cout"]), device=x.device,
+                    dtype=torch.float32)
     lib = L()
     ws = torch.empty(max(lib.conv2d_bn_workspace_bytes(g), 16), device=x.device, dtype=torch.uint8)
     if pro.get("x2") is not None:
-        assert pro["x2"].is_contiguous() and pro["x2"].shape == x.shape
+        assert pro["x2"].is_contiguous() and (regen is not None or pro["x2"].shape == x.shape)
     if "in_relu" in pro:
         pro = dict(pro, in_relu=int(pro["in_relu"]))
     fmt = plane_format(None, w_ohwi)
-    lib.conv2d_fwd(x, w_ohwi, y, g, **pro, ldr=g["Cout"], w_split=split_weights(w_ohwi, fmt),
-                   w_frag=pack_weights(w_ohwi, fmt), bn=(acc, ws), w_format=fmt)
+    more = dict(stats_only=True) if stats_only else {}
+    if regen is not None:
+        x, more["regen"] = _regen_launch(x, regen, pro.get("x2"), fmt)
+    lib.conv2d_fwd(x, w_ohwi, None if stats_only else y, g, **pro, ldr=g["Cout"],
+                   w_split=split_weights(w_ohwi, fmt), w_frag=pack_weights(w_ohwi, fmt), bn=(acc, ws),
+                   w_format=fmt, **more)
     return y
 
 
@@ -228,8 +265,8 @@ def conv2d_bn_train(x, w_ohwi, stride, pad, bn, **pro):
     assert bn.momentum is not None
     acc = _bn_state(bn)
     try:
-        y = conv2d_bn_sums(x, w_ohwi, stride, pad, acc, **pro)
-        return y, bn_finalize_sums(acc, y.numel() // y.size(-1), bn)
+        y = conv2d_bn_sums(x, w_ohwi, stride, pad, acc, **pro)   # (stats_only: y is [N,Ho,Wo,0])
+        return y, bn_finalize_sums(acc, y.size(0) * y.size(1) * y.size(2), bn)
     except Exception:
         # the sums must be zero between launches: a failure between the convolution and the
         # finalize (an allocation, an argument check) would otherwise leak this pass's sums into
