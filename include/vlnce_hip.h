@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 148 = this header */
+int vlnce_version(void); /* major*100 + minor; 149 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -868,6 +868,40 @@ int vlnce_ppo_loss(const float* values, const float* returns, const float* value
                    const float* radians, int B, float clip, float value_coef, float entropy_coef,
                    float pano_coef, float offset_coef, float distance_coef, float reg_coef,
                    int use_clipped, float* stats, float* grads, vlnce_stream_t stream);
+
+/* The imitation-learning objective of BaseVLNCETrainer._update_agent (base_il_trainer.py:159-172)
+ * and its gradient in ONE launch of one workgroup (ABI 149).  logits [T,N,A] fp32 contiguous (rows
+ * time-major, t * N + n; raw or normalised: the log-softmax is taken again, as F.cross_entropy
+ * does), targets [T,N] int64, weights [T,N] fp32, aux a device scalar or NULL, inv_scalar = 1 /
+ * loss_accumulation_scalar.
+ *   ce[t,n]  = logsumexp(logits[t,n,:]) - logits[t,n,targets[t,n]]
+ *   action   = mean_n( sum_t w ce / sum_t w )
+ *   stats[3] = {(action + aux) * inv_scalar, action, aux or 0}
+ *   dlogits [T*N,A] = (softmax - onehot) * w[t,n] / sum_t w[:,n] / N * inv_scalar
+ * (the gradient of stats[0] for a unit upstream gradient; d stats[0] / d aux = inv_scalar).
+ * torch's arithmetic: w * ce is a product (a padded row, w = 0, is multiplied, not skipped: a
+ * non-finite ce there gives NaN), and a column whose weights sum to zero divides 0 / 0.  A target
+ * outside [0, A) reads nothing outside its row: that row's ce and dlogits are NaN, and so are
+ * action and stats[0].  fp64 accumulators, fixed reduction order, no atomics: two runs give the
+ * same bits.  Shapes: T >= 1, 1 <= N <= 1024 (the column sums are kept in LDS), 1 <= A <= 16;
+ * vlnce_il_loss_supported says so, the launch refuses anything else. */
+int vlnce_il_loss_supported(int T, int N, int A);
+int vlnce_il_loss(const float* logits, const int64_t* targets, const float* weights,
+                  const float* aux, float inv_scalar, int T, int N, int A, float* stats,
+                  float* dlogits, vlnce_stream_t stream);
+
+/* The progress monitor's auxiliary term without its [R,E] matrix (ABI 149): F.mse_loss of estimate
+ * [E] against target [R,1] broadcasts to element (i,j) = (e_j - t_i)^2 (cma_policy.py:296-307), and
+ * AuxLosses.reduce's masked_select with a mask [E] picks COLUMNS j (aux_losses.py:24-32):
+ *   value[0]      = sum_j m_j sum_i (e_j - t_i)^2 / (R * sum m)
+ *   d_estimate[j] = m_j * 2 sum_i (e_j - t_i) / (R * sum m)
+ * E != R is allowed (under data parallelism the targets are those of all ranks).  mask: one byte
+ * per column, non-zero = selected; no selected column gives 0 / 0 like the mean of nothing.  The
+ * column sum is evaluated in fp64 as R d^2 - 2 d S1 + S2 around the targets' mean (d = e_j - mean,
+ * S1 = sum_i (t_i - mean), S2 = sum_i (t_i - mean)^2), which does not cancel when the estimates sit
+ * on the targets.  One workgroup, fixed reduction order, no atomics. */
+int vlnce_pair_mse(const float* estimate, const float* target, const uint8_t* mask, int E, int R,
+                   float* value, float* d_estimate, vlnce_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,9 @@ _SIGNATURES = {
     "vlnce_ppo_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _F, _F, _I,
                             _P, _P, _P]),
     "vlnce_ppo_returns": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _F, _I, _P]),
+    "vlnce_il_loss_supported": (_I, [_I, _I, _I]),
+    "vlnce_il_loss": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P]),
+    "vlnce_pair_mse": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "vlnce_space_to_depth2": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vlnce_frames_s2d": (_I, [C.POINTER(Frames), _P, _I, _I, _P, _P, _P]),
     "vlnce_frames_avgpool2": (_I, [C.POINTER(Frames), _P, _P]),
@@ -314,7 +317,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 148  # include/vlnce_hip.h
+    ABI = 149  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -717,6 +720,32 @@ class HipLib:
                                                _ptr(next_value), _ptr(returns), T, N, float(gamma),
                                                float(tau), int(use_gae), _stream()),
                     "vlnce_ppo_returns")
+
+    def il_loss_supported(self, T, N, A):
+        return bool(self.dll.vlnce_il_loss_supported(int(T), int(N), int(A)))
+
+    def il_loss(self, logits, targets, weights, aux, inv_scalar, T, N, A, stats, dlogits):
+        """base_il_trainer.py:159-172 and its gradient in one launch: stats [3] = {loss, action
+        loss, aux}, dlogits [T*N, A] for a unit upstream gradient; aux: a device scalar or None"""
+        assert logits.dtype == torch.float32 and weights.dtype == torch.float32
+        assert targets.dtype == torch.int64 and (aux is None or aux.dtype == torch.float32)
+        assert logits.numel() == T * N * A and targets.numel() == T * N and weights.numel() == T * N
+        assert stats.numel() == 3 and dlogits.numel() == T * N * A
+        assert all(t.is_contiguous() for t in (logits, targets, weights, stats, dlogits))
+        self._check(self.dll.vlnce_il_loss(_ptr(logits), _ptr(targets), _ptr(weights), _ptr(aux),
+                                           float(inv_scalar), T, N, A, _ptr(stats), _ptr(dlogits),
+                                           _stream()), "vlnce_il_loss")
+
+    def pair_mse(self, estimate, target, mask, E, R, value, d_estimate):
+        """mean over the selected columns j of the [R, E] matrix (e_j - t_i)^2, and its gradient
+        wrt the estimates; mask: one byte per column (bool / uint8)"""
+        assert estimate.dtype == torch.float32 and target.dtype == torch.float32
+        assert mask.dtype in (torch.bool, torch.uint8) and mask.numel() == E
+        assert estimate.numel() == E and target.numel() == R and d_estimate.numel() == E
+        assert all(t.is_contiguous() for t in (estimate, target, mask, d_estimate))
+        self._check(self.dll.vlnce_pair_mse(_ptr(estimate), _ptr(target), _ptr(mask), E, R,
+                                            _ptr(value), _ptr(d_estimate), _stream()),
+                    "vlnce_pair_mse")
 
     def space_to_depth2(self, x, y, N, H, W, Cc, pad_lo, pad_hi, scale=None, shift=None):
         self._check(self.dll.vlnce_space_to_depth2(_ptr(x), _ptr(y), N, H, W, Cc, pad_lo, pad_hi,

@@ -41,7 +41,9 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // 147: vlnce_traj_append / vlnce_traj_sensor, vlnce_dagger_mix_actions (DAgger rollout collection on the device).
 // 148: vlnce_epilogue.stats_only (a convolution that takes its BatchNorm statistics and stores no output),
 // vlnce_prologue.regen (a block end that computes conv3's output again instead of reading it), options "r3", "s3_wgs".
-extern "C" int vlnce_version(void) { return 148; }
+// 149: vlnce_il_loss / vlnce_il_loss_supported, vlnce_pair_mse (the imitation-learning objective and the progress
+// monitor's term, each one launch with its gradient).
+extern "C" int vlnce_version(void) { return 149; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)

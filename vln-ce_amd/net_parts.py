@@ -107,6 +107,10 @@ def register_progress_loss(net, features, observations):
     estimate = ops.linear(features, head.weight, head.bias, ops.ACT_TANH).squeeze(1)
     # rows i of the [B, B] loss matrix range over the progress targets of the WHOLE batch: under
     # data parallelism they are gathered from all ranks (AuxLosses.set_data_parallel)
+    if AuxLosses.is_fused():   # the matrix stays its two vectors (AuxLosses.fused)
+        AuxLosses.register_pair_loss("progress_monitor", estimate,
+                                     AuxLosses.gather_rows(observations["progress"]), cfg.alpha)
+        return
     estimate, target = torch.broadcast_tensors(estimate,
                                                AuxLosses.gather_rows(observations["progress"]))
     AuxLosses.register_loss("progress_monitor", (estimate - target) ** 2, cfg.alpha)
