@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 149 = this header */
+int vlnce_version(void); /* major*100 + minor; 150 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -327,10 +327,47 @@ int vlnce_conv2d_fwd(const float* x, const float* w_ohwi, float* y,
  * Replaces nn.Linear / 1x1 nn.Conv1d forward and their dgrad/wgrad
  * (cma_policy.py:103-119,140-170; seq2seq_policy.py:109-121;
  * waypoint_predictors.py:76-180; policy.py:19-21).
+ * Operands: A, B, C and epi->residual need only be 4-byte aligned with any row stride when
+ * transA = transB = 0 (the scalar loaders / the scalar epilogue take what the 16-byte ones cannot);
+ * with transB = 1, B (and with transA = 1 also A) must be 16-byte aligned, else the call is an
+ * error.  epi->scale and epi->shift must be 16-byte aligned whatever route the call takes (the
+ * vectorised epilogue reads four columns of them at once; ABI 150: a 4-byte-aligned view of a
+ * bias is refused with an error, it launches nothing).  transA = 1 requires transB = 1.
  */
 int vlnce_gemm(const float* A, int lda, int transA, const float* B, int ldb, int transB,
                float* C, int ldc, int M, int N, int K,
                const vlnce_epilogue* epi, vlnce_stream_t stream);
+
+/* Which igemm_kernel instance the calling thread's last vlnce_gemm launched and what ran around
+ * it (ABI 150): behind the one entry point sit six loader pairs, three tiles, the split reduction
+ * with its zero-fill and its second bias / activation pass, and the tests name the route a call
+ * must take.  Set by the host code that picks the launch (no device work); -1 before the thread's
+ * first launch; a call refused with an error leaves it as it was.
+ *   bits  0..1  A loader (VLNCE_GEMM_A_*)      bits 2..3  B loader (VLNCE_GEMM_B_*)
+ *   bits  4..5  tile (VLNCE_GEMM_TILE_*, option "igemm_tile"'s numbering)
+ *   bit   6     C was zero-filled first (a split reduction that does not accumulate)
+ *   bit   7     the second pass C = act(C + shift) ran (a split reduction with a bias / activation)
+ *   bits  8..15 split-K factor: K ranges added atomically, 1 = not split */
+#define VLNCE_GEMM_KERNEL(a, b, tile, splitk, zero, pass2) \
+  ((a) | ((b) << 2) | ((tile) << 4) | ((zero) ? 1 << 6 : 0) | ((pass2) ? 1 << 7 : 0) | ((splitk) << 8))
+#define VLNCE_GEMM_KERNEL_A(v) ((v) & 3)
+#define VLNCE_GEMM_KERNEL_B(v) (((v) >> 2) & 3)
+#define VLNCE_GEMM_KERNEL_TILE(v) (((v) >> 4) & 3)
+#define VLNCE_GEMM_KERNEL_ZERO(v) (((v) >> 6) & 1)
+#define VLNCE_GEMM_KERNEL_PASS2(v) (((v) >> 7) & 1)
+#define VLNCE_GEMM_KERNEL_SPLITK(v) (((v) >> 8) & 255)
+#define VLNCE_GEMM_A_BUF 0       /* buffer-descriptor loads: K % 32 == 0, rows 16-byte aligned, < 2 GiB */
+#define VLNCE_GEMM_A_IM2COL_V4 1 /* 16-byte loads: K % 4 == 0, lda % 4 == 0, A 16-byte aligned          */
+#define VLNCE_GEMM_A_IM2COL_S 2  /* 4-byte loads: anything else                                         */
+#define VLNCE_GEMM_A_TRANS 3     /* transA = 1: A stored [K,M]                                          */
+#define VLNCE_GEMM_B_BUF 0       /* [N,K], buffer-descriptor loads */
+#define VLNCE_GEMM_B_NK_V4 1     /* [N,K], 16-byte loads           */
+#define VLNCE_GEMM_B_NK_S 2      /* [N,K], 4-byte loads            */
+#define VLNCE_GEMM_B_KN 3        /* transB = 1: B stored [K,N]     */
+#define VLNCE_GEMM_TILE_128X128 1
+#define VLNCE_GEMM_TILE_128X64 2
+#define VLNCE_GEMM_TILE_64X64 3
+int vlnce_gemm_last_kernel(void);
 
 /* Skinny linear layers (M <= 128 rows = one row per environment; N % 4 == 0, K % 4 == 0; rows of x,
  * w, dy, y 16-byte aligned), ABI 141: y = act(x W^T + b) in ONE launch and the whole backward --

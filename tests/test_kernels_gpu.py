@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_dispatch
+import gemm_dispatch
 import hostsim
 from vlnce_amd import _lib, ops
 
@@ -152,24 +153,26 @@ def test_conv_identity_weight_is_not_transposed(hip):
 
 
 # ------------------------------------------------------------------ gemm
+# (which route each case takes -- loaders, tile, split-K, second pass -- is asserted below against
+# tests/gemm_dispatch.py, not written down here: a comment goes on saying what it said)
 GEMM_CASES = [
     # M, N, K, transA, transB, act, bias
     (64, 256, 2112, 0, 0, 1, True),    # rgb_linear
     (64, 1536, 416, 0, 0, 0, True),    # GRU input projection
     (64, 4, 512, 0, 0, 0, True),       # action head
     (64, 1, 512, 0, 0, 3, True),       # progress monitor (tanh)
-    (640, 512, 50, 0, 0, 0, True),     # instruction x W_ih (K % 4 != 0: scalar loaders)
+    (640, 512, 50, 0, 0, 0, True),     # instruction x W_ih
     (100, 260, 388, 0, 0, 2, True),    # waypoint sizes (sigmoid)
     (64, 512, 256, 0, 1, 0, False),    # dX = dY W
-    (70, 50, 36, 0, 1, 0, False),      # dX ragged, scalar A
+    (70, 50, 36, 0, 1, 0, False),      # dX ragged
     (256, 2112, 64, 1, 1, 0, False),   # dW = dY^T X
     (4, 512, 64, 1, 1, 0, False),      # dW of the action head
     (1, 512, 37, 1, 1, 0, False),      # dW of a 1-output head, ragged K
-    (5000, 256, 256, 0, 0, 0, True),   # text_k over B*L rows (128-row tiles)
-    (40000, 64, 64, 0, 0, 0, False),   # M > 32767: row folding
-    (512, 50, 5120, 1, 1, 0, False),   # dW_ih of the instruction RNN: split-K over L*B rows
-    (64, 128, 3072, 0, 0, 1, True),    # depth_linear: split-K + bias/ReLU second pass
-    (64, 416, 1536, 0, 1, 0, False),   # dX of the GRU input projection: split-K
+    (5000, 256, 256, 0, 0, 0, True),   # text_k over B*L rows
+    (40000, 64, 64, 0, 0, 0, False),   # M > 32767 (row folding)
+    (512, 50, 5120, 1, 1, 0, False),   # dW_ih of the instruction RNN over L*B rows
+    (64, 128, 3072, 0, 0, 1, True),    # depth_linear
+    (64, 416, 1536, 0, 1, 0, False),   # dX of the GRU input projection
 ]
 
 
@@ -182,6 +185,9 @@ def test_gemm(hip, case):
     t = dict(A=A, B=B, Cm=torch.zeros(M, N), shift=rnd(N, seed=3) if bias else None)
     sc = dict(lda=A.size(1), transA=ta, ldb=B.size(1), transB=tb, ldc=N, M=M, N=N, K=K, act=act)
     cpu, gpu = both("gemm", t, sc)
+    got = hip.gemm_last_kernel()
+    want = gemm_dispatch.expected(gemm_dispatch.Call(M, N, K, ta, tb, shift=bias, act=act))
+    assert got == want, (case, "ran on", got, "the dispatch rules say", want)
     close(gpu["Cm"], cpu["Cm"], what=str(case))
 
 

@@ -68,6 +68,23 @@ def decode_wgrad_kernel(v):
     return None if v < 0 else WgradKernel(v & 15, (v >> 4) & 255, bool((v >> 12) & 1))
 
 
+# ---- vlnce_gemm_last_kernel (VLNCE_GEMM_KERNEL of the header), as names
+GemmKernel = collections.namedtuple("GemmKernel", "a b tile splitk zero pass2")
+GemmKernel.__doc__ = """a: the A loader "buf" | "v4" | "s" | "trans"; b: the B loader "buf" | "nk_v4" | "nk_s" | "kn";
+tile: (rows, columns) of the igemm_kernel instance; splitk: the split-K factor (1 = not split); zero: C was
+zero-filled first; pass2: the second bias / activation pass ran"""
+_GEMM_A = ("buf", "v4", "s", "trans")
+_GEMM_B = ("buf", "nk_v4", "nk_s", "kn")
+_GEMM_TILES = (None, (128, 128), (128, 64), (64, 64))
+
+
+def decode_gemm_kernel(v):
+    if v < 0:
+        return None
+    return GemmKernel(_GEMM_A[v & 3], _GEMM_B[(v >> 2) & 3], _GEMM_TILES[(v >> 4) & 3], (v >> 8) & 255,
+                      bool((v >> 6) & 1), bool((v >> 7) & 1))
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(n, _I) for n in
                 ("N", "H", "W", "Cin", "Cout", "KH", "KW", "stride", "pad", "Ho", "Wo", "ldx", "ldy")]
@@ -127,6 +144,7 @@ _SIGNATURES = {
     "vlnce_conv2d_wgrad_last_path": (_I, []),
     "vlnce_conv2d_last_kernel": (_I, []),
     "vlnce_conv2d_wgrad_last_kernel": (_I, []),
+    "vlnce_gemm_last_kernel": (_I, []),
     "vlnce_embedding_bwd": (_I, [_P, _P, _P, _L, _I, _L, _L, _P]),
     "vlnce_conv2d_pack_bytes": (C.c_long, [C.POINTER(ConvDesc)]),
     "vlnce_conv2d_pack_weights": (_I, [_P, _P, C.POINTER(ConvDesc), _I, _P]),
@@ -317,7 +335,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 149  # include/vlnce_hip.h
+    ABI = 150  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -572,6 +590,10 @@ class HipLib:
                        int(accumulate), None)
         self._check(self.dll.vlnce_gemm(_ptr(A), lda, transA, _ptr(B), ldb, transB, _ptr(Cm), ldc,
                                         M, N, K, C.byref(epi), _stream()), "vlnce_gemm")
+
+    def gemm_last_kernel(self):
+        """the route the calling thread's last gemm took, decoded (GemmKernel)"""
+        return decode_gemm_kernel(int(self.dll.vlnce_gemm_last_kernel()))
 
     def colsum(self, x, ldx, M, N, out, accumulate=0):
         self._check(self.dll.vlnce_colsum(_ptr(x), ldx, M, N, _ptr(out), accumulate, _stream()),

@@ -43,7 +43,10 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // vlnce_prologue.regen (a block end that computes conv3's output again instead of reading it), options "r3", "s3_wgs".
 // 149: vlnce_il_loss / vlnce_il_loss_supported, vlnce_pair_mse (the imitation-learning objective and the progress
 // monitor's term, each one launch with its gradient).
-extern "C" int vlnce_version(void) { return 149; }
+// 150: vlnce_gemm_last_kernel (which igemm_kernel instance the thread's last vlnce_gemm launched: loader pair,
+// tile, split-K factor, zero-fill, second pass; VLNCE_GEMM_KERNEL).  vlnce_gemm refuses a scale / shift that
+// is not 16-byte aligned, and refuses every bad argument before it launches anything.
+extern "C" int vlnce_version(void) { return 150; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)

@@ -1218,11 +1218,20 @@ TileChoice choose_tile(long M, int N) {
   return {64, 64};
 }
 
+// tile_out (vlnce_gemm's route record): the tile of the instance launched, in option
+// "igemm_tile"'s numbering
 template <int AMODE, int BMODE>
-int dispatch_tiles(const IgemmParams& p, hipStream_t s) {
+int dispatch_tiles(const IgemmParams& p, hipStream_t s, int* tile_out = nullptr) {
   const TileChoice t = choose_tile(p.M, p.N);
-  if (t.bm == 128 && t.bn == 128) return launch<128, 128, 2, 2, AMODE, BMODE>(p, s);
-  if (t.bm == 128 && t.bn == 64) return launch<128, 64, 2, 2, AMODE, BMODE>(p, s);
+  if (t.bm == 128 && t.bn == 128) {
+    if (tile_out) *tile_out = VLNCE_GEMM_TILE_128X128;
+    return launch<128, 128, 2, 2, AMODE, BMODE>(p, s);
+  }
+  if (t.bm == 128 && t.bn == 64) {
+    if (tile_out) *tile_out = VLNCE_GEMM_TILE_128X64;
+    return launch<128, 64, 2, 2, AMODE, BMODE>(p, s);
+  }
+  if (tile_out) *tile_out = VLNCE_GEMM_TILE_64X64;
   return launch<64, 64, 2, 2, AMODE, BMODE>(p, s);
 }
 int dispatch_dual(const IgemmParams& p, hipStream_t s) {
@@ -1232,7 +1241,8 @@ int dispatch_dual(const IgemmParams& p, hipStream_t s) {
   return launch<64, 64, 2, 2, A_BUF, B_BUF, 0, 0, 1>(p, s);
 }
 template <int AMODE, int BMODE>
-int dispatch_small(const IgemmParams& p, hipStream_t s) {
+int dispatch_small(const IgemmParams& p, hipStream_t s, int* tile_out = nullptr) {
+  if (tile_out) *tile_out = VLNCE_GEMM_TILE_64X64;
   return launch<64, 64, 2, 2, AMODE, BMODE>(p, s);
 }
 // buffer-descriptor hot path: channels-last im2col / row-major A with Cin % 32 == 0, at most
@@ -1737,12 +1747,24 @@ extern "C" int vlnce_conv2d_fwd(const float* x, const float* w, float* y, const 
   return bn_finalize_behind(dispatch_tiles<A_IM2COL_S, B_NK_S>(p, s));
 }
 
+// which igemm_kernel instance the thread's last vlnce_gemm launched (VLNCE_GEMM_KERNEL)
+static thread_local int g_gemm_last_kernel = -1;
+extern "C" int vlnce_gemm_last_kernel(void) { return g_gemm_last_kernel; }
+
 extern "C" int vlnce_gemm(const float* A, int lda, int transA, const float* B, int ldb, int transB,
                           float* C, int ldc, int M, int N, int K, const vlnce_epilogue* epi,
                           vlnce_stream_t stream) {
   VLNCE_CHECK_ARG(A && B && C, "gemm: null argument");
   VLNCE_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: bad shape %d %d %d", M, N, K);
   VLNCE_CHECK_ARG(!(epi && epi->stat_partial), "gemm: stat_partial is a conv-only option");
+  // the vectorised epilogue reads four columns of scale / shift as one 16-byte vector
+  VLNCE_CHECK_ARG(!epi || (aligned16(epi->scale) && aligned16(epi->shift)),
+                  "gemm: scale / shift must be 16-byte aligned");
+  // (refused before anything is launched: a split reduction zero-fills C ahead of the dispatch)
+  VLNCE_CHECK_ARG(!transA || transB,
+                  "gemm: transA requires transB (only A^T * B^T-stored form is built)");
+  VLNCE_CHECK_ARG(!transB || aligned16(B), "gemm: B must be 16-byte aligned");
+  VLNCE_CHECK_ARG(!transA || aligned16(A), "gemm: operands must be 16-byte aligned");
   IgemmParams p{};
   p.A = A;
   p.B = B;
@@ -1776,43 +1798,55 @@ extern "C" int vlnce_gemm(const float* A, int lda, int transA, const float* B, i
   if (plain) p.splitk = choose_splitk(p, transA != 0);
   const float* bias2 = nullptr;
   int act2 = 0;
+  bool zero_fill = false;
   if (p.splitk > 1) {
     bias2 = p.shift;
     act2 = p.act;
     p.shift = nullptr;
     p.act = 0;
     if (!p.accumulate) vlnce_zero(C, M, N, ldc, s);
+    zero_fill = !p.accumulate;
     p.accumulate = 0;
   }
-  int rc;
+  int rc, tile = 0, la, lb;  // the route record: tile and loader pair of the branch that launches
   if (!transA) {
     const bool av4 = (K % 4 == 0) && (lda % 4 == 0) && aligned16(A);
     if (!transB) {
       const bool bv4 = (K % 4 == 0) && (ldb % 4 == 0) && aligned16(B);
       p.a_bytes = (((long)M - 1) * lda + K) * 4;
       p.b_bytes = (((long)N - 1) * ldb + K) * 4;
-      if (av4 && bv4 && buf_ok(p))
-        rc = p.splitk > 1 ? dispatch_small<A_BUF, B_BUF>(p, s) : dispatch_tiles<A_BUF, B_BUF>(p, s);
-      else if (av4 && bv4)
-        rc = p.splitk > 1 ? dispatch_small<A_IM2COL_V4, B_NK_V4>(p, s)
-                          : dispatch_tiles<A_IM2COL_V4, B_NK_V4>(p, s);
-      else
-        rc = dispatch_small<A_IM2COL_S, B_NK_S>(p, s);
+      if (av4 && bv4 && buf_ok(p)) {
+        la = VLNCE_GEMM_A_BUF, lb = VLNCE_GEMM_B_BUF;
+        rc = p.splitk > 1 ? dispatch_small<A_BUF, B_BUF>(p, s, &tile)
+                          : dispatch_tiles<A_BUF, B_BUF>(p, s, &tile);
+      } else if (av4 && bv4) {
+        la = VLNCE_GEMM_A_IM2COL_V4, lb = VLNCE_GEMM_B_NK_V4;
+        rc = p.splitk > 1 ? dispatch_small<A_IM2COL_V4, B_NK_V4>(p, s, &tile)
+                          : dispatch_tiles<A_IM2COL_V4, B_NK_V4>(p, s, &tile);
+      } else {
+        la = VLNCE_GEMM_A_IM2COL_S, lb = VLNCE_GEMM_B_NK_S;
+        rc = dispatch_small<A_IM2COL_S, B_NK_S>(p, s, &tile);
+      }
     } else {
-      VLNCE_CHECK_ARG(aligned16(B), "gemm: B must be 16-byte aligned");
-      if (av4)
-        rc = p.splitk > 1 ? dispatch_small<A_IM2COL_V4, B_KN>(p, s)
-                          : dispatch_tiles<A_IM2COL_V4, B_KN>(p, s);
-      else
-        rc = dispatch_small<A_IM2COL_S, B_KN>(p, s);
+      lb = VLNCE_GEMM_B_KN;
+      if (av4) {
+        la = VLNCE_GEMM_A_IM2COL_V4;
+        rc = p.splitk > 1 ? dispatch_small<A_IM2COL_V4, B_KN>(p, s, &tile)
+                          : dispatch_tiles<A_IM2COL_V4, B_KN>(p, s, &tile);
+      } else {
+        la = VLNCE_GEMM_A_IM2COL_S;
+        rc = dispatch_small<A_IM2COL_S, B_KN>(p, s, &tile);
+      }
     }
   } else {
-    VLNCE_CHECK_ARG(transB, "gemm: transA requires transB (only A^T * B^T-stored form is built)");
-    VLNCE_CHECK_ARG(aligned16(A) && aligned16(B), "gemm: operands must be 16-byte aligned");
-    rc = p.splitk > 1 ? dispatch_small<A_TRANS, B_KN>(p, s) : dispatch_tiles<A_TRANS, B_KN>(p, s);
+    la = VLNCE_GEMM_A_TRANS, lb = VLNCE_GEMM_B_KN;
+    rc = p.splitk > 1 ? dispatch_small<A_TRANS, B_KN>(p, s, &tile)
+                      : dispatch_tiles<A_TRANS, B_KN>(p, s, &tile);
   }
+  const bool pass2 = p.splitk > 1 && (bias2 || act2);
+  g_gemm_last_kernel = VLNCE_GEMM_KERNEL(la, lb, tile, p.splitk, zero_fill, pass2);
   if (rc != 0) return rc;
-  if (p.splitk > 1 && (bias2 || act2)) {
+  if (pass2) {
     const long work = (long)M * N;
     const int grid = (int)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256);
     hipLaunchKernelGGL(bias_act_kernel, dim3(grid), dim3(256), 0, s, C, ldc, M, N, bias2, act2);
