@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 150 = this header */
+int vlnce_version(void); /* major*100 + minor; 151 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -69,6 +69,9 @@ const char* vlnce_last_error(void);
  *                               kernel covers
  *   "s3_wgs"           0        conv_s3_kernel / conv_r3_kernel: 0 = one workgroup per CU; n > 0 = at most n
  *                               workgroups (tests: many tiles per workgroup at a small M)
+ *   "waypoint_dist"    0        read by the HOST (ABI 151): 1 = WaypointPolicy.evaluate_actions computes its
+ *                               log-probability and entropies through vlnce_waypoint_eval / _bwd instead of
+ *                               torch's distribution classes (the same as policy.fused_distributions = True)
  * Set options between launches, not concurrently with them (relaxed atomics).  Unknown names
  * return non-zero. */
 int vlnce_set_option(const char* name, int value);
@@ -939,6 +942,95 @@ int vlnce_il_loss(const float* logits, const int64_t* targets, const float* weig
  * on the targets.  One workgroup, fixed reduction order, no atomics. */
 int vlnce_pair_mse(const float* estimate, const float* target, const uint8_t* mask, int E, int R,
                    float* value, float* d_estimate, vlnce_stream_t stream);
+
+/* The distribution arithmetic of WaypointPolicy.evaluate_actions (waypoint_policy.py:258-347 over
+ * TruncatedNormal / CustomFixedCategorical of models/utils.py:24-152, 269-289) as ONE launch forward
+ * and ONE backward (ABI 151): the composite log-probability and the three entropies of a stored
+ * action under the heads' outputs.  One thread per row, every row in fp64, one rounding to fp32 at
+ * each store, no floating-point atomics: two runs give the same bits.
+ *
+ * A component ("offset", "distance") is described by a vlnce_wp_part:
+ *   kind     VLNCE_WP_ABSENT (contributes nothing, its entropy is 0), VLNCE_WP_CONTINUOUS (truncated
+ *            normal on [lo, hi]) or VLNCE_WP_DISCRETE (categorical over K classes)
+ *   first    [B,P] means, or [B,P,K] logits (raw or normalised)
+ *   second   [B,P] variances (continuous only)
+ *   element  the stored sub-action: float [B] (continuous) or int64 [B] (class index)
+ *   lo, hi   the truncation window, as fp32 (what torch's fp32 arithmetic makes of the Python floats)
+ *   weight   the 0 / 1 `predict_*` switch
+ * With c = pano[b] (int64, 0..P; P = STOP), h = c mod P and gate = (c != P):
+ *   out[0][b] = log_softmax(logits[b,:])[c] + sum_part gate * weight * logp_part(element[b])
+ *   out[1][b] = the categorical entropy of logits[b,:]  (a class of probability 0 contributes 0)
+ *   out[2][b] = gate * weight * H_offset,   out[3][b] = gate * weight * H_distance   (continuous)
+ * out is one float buffer: log_prob [B], pano entropy [B], then the offset's and the distance's
+ * entropy blocks.  A continuous (or absent) part's block is [B] as above.  A DISCRETE part's block is
+ * [B][B], E[i][j] = gate_i * weight * H_j: the reference multiplies its [B,1] weight with the
+ * categorical's [B] entropy, which broadcasts (for B = 1 the one value); E[i][j] is NaN where row j
+ * is flagged or pano[i] is out of range, and its gradient reaches row j as sum_i gate_i weight g[i][j]
+ * (rows in order).  out_floats = the buffer's capacity (>= B (2 + n + n), n = 1 or B; checked).
+ * continuous, with loc = first[b,h], scale = sqrt(second[b,h]), [a, b] = ([lo, hi] - loc) / scale,
+ * mass = cdf(b) - cdf(a), z = (element - loc) / scale:
+ *   logp = -z^2 / 2 - log(sqrt(2 pi) scale mass)
+ *   H    = log(sqrt(2 pi e) scale mass) + (a pdf(a) - b pdf(b)) / (2 mass)
+ * discrete: logp / H of the categorical over first[b,h,:].  gate * weight MULTIPLIES a value that was
+ * computed (torch's arithmetic: 0 * inf is NaN); a weight-0 or STOP row is not skipped.
+ *
+ * flags[b] (int32) collects what the reference asserts on, whatever the row's weight:
+ * VLNCE_WP_FLAG_PANO (pano outside [0, P]), and per component, shifted left by
+ * VLNCE_WP_FLAG_SHIFT_OFFSET / _DISTANCE: VLNCE_WP_FLAG_LOC (loc outside the window, or NaN),
+ * VLNCE_WP_FLAG_ELEMENT (element outside the window), VLNCE_WP_FLAG_VARIANCE (sqrt(variance) >= 0
+ * fails), VLNCE_WP_FLAG_CLASS (class index outside [0, K)).  A flagged row is NaN in every output
+ * and every gradient of that row, and nothing is read through its out-of-range index.
+ *
+ * saved [S][B] fp32 holds the partial derivatives (gate * weight folded in) the backward multiplies
+ * with the incoming gradients (a discrete part's entropy planes without gate * weight, which its
+ * backward takes from pano): S = 2 (P + 1) + n(offset) + n(distance), n = 0 / 4 / 2 K for an
+ * absent / continuous / discrete part; saved_floats = the buffer's capacity (>= S * B, checked).
+ *
+ * vlnce_waypoint_eval_bwd: g_* = the gradient arriving at each block of out, in the block's shape
+ * (NULL = zero); vlnce_wp_part_grad repeats the part's kind, K and weight; writes the DENSE
+ * gradients d_logits [B,P+1] and, per part, d_first (shape of first) and d_second [B,P] (continuous
+ * only) -- the zeros outside the chosen heading included, so nothing is zero-filled first.
+ *
+ * Shapes: B >= 1, 1 <= P <= 63, K <= 32 per discrete part (K_* = 0 for a part that is not discrete);
+ * vlnce_waypoint_eval_supported says so, and both launches refuse anything else, and null pointers,
+ * before they launch. */
+enum { VLNCE_WP_ABSENT = 0, VLNCE_WP_CONTINUOUS = 1, VLNCE_WP_DISCRETE = 2 };
+enum {
+  VLNCE_WP_FLAG_PANO = 1,
+  VLNCE_WP_FLAG_LOC = 1,
+  VLNCE_WP_FLAG_ELEMENT = 2,
+  VLNCE_WP_FLAG_VARIANCE = 4,
+  VLNCE_WP_FLAG_CLASS = 8,
+  VLNCE_WP_FLAG_SHIFT_OFFSET = 4,
+  VLNCE_WP_FLAG_SHIFT_DISTANCE = 8
+};
+typedef struct {
+  int kind;
+  int K;
+  float lo;
+  float hi;
+  float weight;
+  const float* first;
+  const float* second;
+  const void* element;
+} vlnce_wp_part;
+typedef struct {
+  int kind;
+  int K;
+  float weight;
+  float* d_first;
+  float* d_second;
+} vlnce_wp_part_grad;
+int vlnce_waypoint_eval_supported(int B, int P, int K_offset, int K_distance);
+int vlnce_waypoint_eval(const float* logits, const int64_t* pano, const vlnce_wp_part* offset,
+                        const vlnce_wp_part* distance, int B, int P, float* out,
+                        long out_floats, float* saved, long saved_floats, int32_t* flags,
+                        vlnce_stream_t stream);
+int vlnce_waypoint_eval_bwd(const float* g_logp, const float* g_ent_pano, const float* g_ent_offset,
+                            const float* g_ent_distance, const int64_t* pano, const float* saved,
+                            const int32_t* flags, const vlnce_wp_part_grad* offset,
+                            const vlnce_wp_part_grad* distance, int B, int P, float* d_logits,
+                            vlnce_stream_t stream);
 
 #ifdef __cplusplus
 }

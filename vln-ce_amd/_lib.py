@@ -127,6 +127,36 @@ class TrajSensor(C.Structure):   # vlnce_traj_sensor
                 ("C", _I), ("P", _I), ("src_dtype", _I), ("dst_dtype", _I)]
 
 
+class WpPart(C.Structure):   # vlnce_wp_part
+    _fields_ = [("kind", _I), ("K", _I), ("lo", _F), ("hi", _F), ("weight", _F), ("first", _P),
+                ("second", _P), ("element", _P)]
+
+
+class WpPartGrad(C.Structure):   # vlnce_wp_part_grad
+    _fields_ = [("kind", _I), ("K", _I), ("weight", _F), ("d_first", _P), ("d_second", _P)]
+
+
+# ---- vlnce_waypoint_eval: one component (offset / distance) of the Waypoint action, as tensors
+WP_ABSENT, WP_CONTINUOUS, WP_DISCRETE = 0, 1, 2
+WP_FLAG_PANO = 1
+WP_FLAG_LOC, WP_FLAG_ELEMENT, WP_FLAG_VARIANCE, WP_FLAG_CLASS = 1, 2, 4, 8   # << the part's shift
+WP_FLAG_SHIFT = {"offset": 4, "distance": 8}
+WaypointPart = collections.namedtuple("WaypointPart", "kind K lo hi weight first second element")
+WaypointPartGrad = collections.namedtuple("WaypointPartGrad", "kind K weight d_first d_second")
+
+
+def waypoint_saved_planes(P, parts):
+    """S of vlnce_waypoint_eval's saved [S, B]: 2 (P + 1) + per part 0 / 4 / 2 K"""
+    return 2 * (P + 1) + sum(4 if p.kind == WP_CONTINUOUS else 2 * p.K if p.kind == WP_DISCRETE else 0
+                             for p in parts)
+
+
+def waypoint_entropy_floats(B, part):
+    """size of a part's entropy block in vlnce_waypoint_eval's out: [B], or the reference's [B, B]
+    broadcast for a discrete part"""
+    return B * B if part.kind == WP_DISCRETE else B
+
+
 class Epilogue(C.Structure):
     _fields_ = [("scale", _P), ("shift", _P), ("residual", _P), ("ldr", _I), ("act", _I),
                 ("accumulate", _I), ("stat_partial", _P), ("bn", C.POINTER(BnSums)),
@@ -180,6 +210,11 @@ _SIGNATURES = {
     "vlnce_il_loss_supported": (_I, [_I, _I, _I]),
     "vlnce_il_loss": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P]),
     "vlnce_pair_mse": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    "vlnce_waypoint_eval_supported": (_I, [_I, _I, _I, _I]),
+    "vlnce_waypoint_eval": (_I, [_P, _P, C.POINTER(WpPart), C.POINTER(WpPart), _I, _I, _P, _L, _P, _L, _P,
+                                 _P]),
+    "vlnce_waypoint_eval_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(WpPartGrad),
+                                     C.POINTER(WpPartGrad), _I, _I, _P, _P]),
     "vlnce_space_to_depth2": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vlnce_frames_s2d": (_I, [C.POINTER(Frames), _P, _I, _I, _P, _P, _P]),
     "vlnce_frames_avgpool2": (_I, [C.POINTER(Frames), _P, _P]),
@@ -335,7 +370,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 150  # include/vlnce_hip.h
+    ABI = 151  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -355,7 +390,7 @@ class HipLib:
     # the VLNCE_* variables of INTEGRATION.md section 8 are translated here, once, at load
     OPTION_NAMES = ("conv_math", "p3", "p3_tile", "s3", "u3", "u3_waves", "x3_tile", "igemm_tile",
                     "igemm_nobuf", "igemm_no_splitk", "wgrad_tile", "rollout_one_xcd", "m3", "r3",
-                    "s3_wgs")
+                    "s3_wgs", "waypoint_dist")
 
     def _options_from_env(self):
         for name in self.OPTION_NAMES:
@@ -768,6 +803,60 @@ class HipLib:
         self._check(self.dll.vlnce_pair_mse(_ptr(estimate), _ptr(target), _ptr(mask), E, R,
                                             _ptr(value), _ptr(d_estimate), _stream()),
                     "vlnce_pair_mse")
+
+    def waypoint_eval_supported(self, B, P, K_offset, K_distance):
+        return bool(self.dll.vlnce_waypoint_eval_supported(int(B), int(P), int(K_offset),
+                                                           int(K_distance)))
+
+    def waypoint_eval(self, logits, pano, offset, distance, B, P, out, saved, flags):
+        """waypoint_policy.py:258-347's distribution arithmetic in one launch: offset / distance are
+        WaypointPart tuples; out = {log_prob [B], pano entropy [B], offset / distance entropy blocks
+        of waypoint_entropy_floats()}, saved [waypoint_saved_planes(), B] the partial derivatives for
+        waypoint_eval_bwd, flags [B] int32"""
+        assert logits.dtype == torch.float32 and pano.dtype == torch.int64 and out.dtype == torch.float32
+        assert logits.numel() == B * (P + 1) and pano.numel() == B
+        assert flags.dtype == torch.int32 and flags.numel() == B and saved.dtype == torch.float32
+        assert all(t.is_contiguous() for t in (logits, pano, out, saved, flags))
+        descs = []
+        for p in (offset, distance):   # (a missing tensor of a present part goes through as NULL: refused)
+            n = B * P * (p.K if p.kind == WP_DISCRETE else 1)
+            elem = torch.float32 if p.kind == WP_CONTINUOUS else torch.int64
+            assert p.first is None or (p.first.dtype == torch.float32 and p.first.numel() == n
+                                       and p.first.is_contiguous())
+            assert p.second is None or (p.second.dtype == torch.float32 and p.second.numel() == B * P
+                                        and p.second.is_contiguous())
+            assert p.element is None or (p.element.dtype == elem and p.element.numel() == B
+                                         and p.element.is_contiguous())
+            descs.append(WpPart(int(p.kind), int(p.K), float(p.lo), float(p.hi), float(p.weight),
+                                _ptr(p.first), _ptr(p.second), _ptr(p.element)))
+        self._check(self.dll.vlnce_waypoint_eval(
+            _ptr(logits), _ptr(pano), C.byref(descs[0]), C.byref(descs[1]), B, P, _ptr(out),
+            out.numel(), _ptr(saved), saved.numel(), _ptr(flags), _stream()), "vlnce_waypoint_eval")
+
+    def waypoint_eval_bwd(self, grads, pano, saved, flags, offset, distance, B, P, d_logits):
+        """grads: the four gradients arriving at the blocks of out (None = zero); offset / distance:
+        WaypointPartGrad tuples whose d_first / d_second are written DENSE, as is d_logits [B, P+1]"""
+        sizes = (B, B, waypoint_entropy_floats(B, offset), waypoint_entropy_floats(B, distance))
+        assert len(grads) == 4 and all(g is None or (g.dtype == torch.float32 and g.numel() == n
+                                                     and g.is_contiguous())
+                                       for g, n in zip(grads, sizes))
+        assert d_logits.dtype == torch.float32 and d_logits.numel() == B * (P + 1)
+        assert d_logits.is_contiguous() and saved.is_contiguous() and flags.dtype == torch.int32
+        descs = []
+        for p in (offset, distance):
+            n = B * P * (p.K if p.kind == WP_DISCRETE else 1)
+            assert p.d_first is None or (p.d_first.dtype == torch.float32 and p.d_first.numel() == n
+                                         and p.d_first.is_contiguous())
+            assert p.d_second is None or (p.d_second.dtype == torch.float32
+                                          and p.d_second.numel() == B * P and p.d_second.is_contiguous())
+            descs.append(WpPartGrad(int(p.kind), int(p.K), float(p.weight), _ptr(p.d_first),
+                                    _ptr(p.d_second)))
+        assert saved.numel() >= B * (2 * (P + 1) + sum(
+            4 if p.kind == WP_CONTINUOUS else 2 * p.K if p.kind == WP_DISCRETE else 0
+            for p in (offset, distance)))
+        self._check(self.dll.vlnce_waypoint_eval_bwd(
+            *[_ptr(g) for g in grads], _ptr(pano), _ptr(saved), _ptr(flags), C.byref(descs[0]),
+            C.byref(descs[1]), B, P, _ptr(d_logits), _stream()), "vlnce_waypoint_eval_bwd")
 
     def space_to_depth2(self, x, y, N, H, W, Cc, pad_lo, pad_hi, scale=None, shift=None):
         self._check(self.dll.vlnce_space_to_depth2(_ptr(x), _ptr(y), N, H, W, Cc, pad_lo, pad_hi,

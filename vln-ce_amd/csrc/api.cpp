@@ -46,7 +46,9 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // 150: vlnce_gemm_last_kernel (which igemm_kernel instance the thread's last vlnce_gemm launched: loader pair,
 // tile, split-K factor, zero-fill, second pass; VLNCE_GEMM_KERNEL).  vlnce_gemm refuses a scale / shift that
 // is not 16-byte aligned, and refuses every bad argument before it launches anything.
-extern "C" int vlnce_version(void) { return 150; }
+// 151: vlnce_waypoint_eval / _bwd / _supported, vlnce_wp_part (WaypointPolicy.evaluate_actions' distribution
+// arithmetic: one launch forward, one backward, no host synchronisation); option "waypoint_dist".
+extern "C" int vlnce_version(void) { return 151; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)
@@ -59,10 +61,10 @@ const OptDef kOpts[VLNCE_OPT_COUNT] = {
     {"conv_math", 2},   {"p3", 2},          {"p3_tile", 0},         {"s3", 1},
     {"u3", 1},          {"u3_waves", 8},    {"x3_tile", 0},         {"igemm_tile", 0},
     {"igemm_nobuf", 0}, {"igemm_no_splitk", 0}, {"wgrad_tile", 64}, {"rollout_one_xcd", 0},
-    {"m3", 1},          {"r3", 1},          {"s3_wgs", 0},
+    {"m3", 1},          {"r3", 1},          {"s3_wgs", 0},          {"waypoint_dist", 0},
 };
 std::atomic<int> g_opt[VLNCE_OPT_COUNT] = {
-    {2}, {2}, {0}, {1}, {1}, {8}, {0}, {0}, {0}, {0}, {64}, {0}, {1}, {1}, {0},
+    {2}, {2}, {0}, {1}, {1}, {8}, {0}, {0}, {0}, {0}, {64}, {0}, {1}, {1}, {0}, {0},
 };
 int opt_index(const char* name) {
   if (name)

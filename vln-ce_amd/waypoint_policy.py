@@ -6,7 +6,10 @@ Plugin-surface mirror of vlnce_baselines/models/waypoint_policy.py:19-347 (`from
 `get_value`, `evaluate_actions` and their return tuples are what ddppo_waypoint_trainer.py and
 WDDPPO call).  The two sub-actions are handled by ONE table-driven code path here instead of a
 pair of parallel methods each; the distribution math is O(N x 13) scalars and stays in torch
-(SURVEY.md 2.1), the net runs on the HIP kernels.
+(SURVEY.md 2.1), the net runs on the HIP kernels.  Opt-in (`fused_distributions`): evaluate_actions
+computes its log-probability and entropies in one HIP launch, and one more backward, with no host
+synchronisation (waypoint_dist.py); the reference's assertions are then read on demand
+(`check_eval_flags`).
 """
 import math
 from typing import NamedTuple
@@ -14,6 +17,7 @@ from typing import NamedTuple
 import torch
 
 from .policy import Policy
+from . import ops, waypoint_dist
 from .registry import baseline_registry
 from .utils import CustomFixedCategorical, TruncatedNormal, batched_index_select
 from .waypoint_predictors import WaypointPredictionNet
@@ -39,12 +43,17 @@ class WaypointPolicy(Policy):
         "offset": ("continuous_offset", "predict_offset", 0.0, 0.0),
     }
 
+    # True: evaluate_actions takes the one-launch path (also switched on by the dispatch option
+    # "waypoint_dist" / VLNCE_WAYPOINT_DIST=1); a shape the kernel does not cover keeps the torch path
+    fused_distributions = False
+
     def __init__(self, observation_space, action_space, model_config):
         net = WaypointPredictionNet(observation_space=observation_space, model_config=model_config)
         super().__init__(net, 1)  # the inherited 1-way action head is never used (App. B-6)
         self._config = model_config
         self.wypt_cfg = model_config.WAYPOINT
         self._offset_limit = math.pi / model_config.num_panos
+        self.eval_flags = None   # int32 [B] of the last fused evaluate_actions (check_eval_flags)
 
     @classmethod
     def from_config(cls, config, observation_space, action_space):
@@ -129,8 +138,55 @@ class WaypointPolicy(Policy):
         features = self.net(observations, rnn_states, prev_actions, masks)[5]
         return self.critic(features)
 
+    # ------------------------------------------------------------------ one-launch evaluate_actions
+    def _eval_spec(self):
+        """(P, {part: (kind, K, lo, hi, predict weight)}) of vlnce_waypoint_eval for this configuration"""
+        kinds = {}
+        for part, (continuous, enabled, _, _) in self._PARTS.items():
+            lo, hi = self._bounds(part)
+            weight = float(bool(getattr(self.wypt_cfg, enabled)))
+            if getattr(self.wypt_cfg, continuous):
+                kinds[part] = (waypoint_dist.WP_CONTINUOUS, 0, lo, hi, weight)
+            else:
+                K = self.wypt_cfg.discrete_distances if part == "distance" else self.wypt_cfg.discrete_offsets
+                kinds[part] = (waypoint_dist.WP_DISCRETE, int(K), 0.0, 0.0, weight)
+        return self._config.num_panos, kinds
+
+    def _fused_eval(self, batch):
+        """the spec when this call takes the one-launch path, else None"""
+        lib = ops.L()
+        if not (self.fused_distributions or (hasattr(lib, "effective_option")
+                                             and lib.effective_option("waypoint_dist"))):
+            return None
+        P, kinds = spec = self._eval_spec()
+        if not lib.waypoint_eval_supported(batch, P, kinds["offset"][1], kinds["distance"][1]):
+            return None
+        return spec
+
+    def check_eval_flags(self):
+        """The reference's assertions on the rows of the last fused evaluate_actions (models/utils.py:
+        46-52, 130-136), raised here -- ONE read-back, on demand -- instead of inside the call."""
+        if self.eval_flags is None:
+            return
+        bits = 0
+        for v in self.eval_flags.tolist():
+            bits |= v
+        msg = waypoint_dist.flag_errors(bits, {p: self._bounds(p) for p in self._PARTS})
+        if msg is not None:
+            raise AssertionError(msg)
+
     def evaluate_actions(self, observations, rnn_states, prev_actions, masks, action_components):
         n_pano = self._config.num_panos
+        spec = self._fused_eval(action_components["pano"].shape[0])
+        if spec is not None:
+            (logits, off_a, off_b, dist_a, dist_b, features, rnn_states_out) = self.net(
+                observations, rnn_states, prev_actions, masks, raw_pano_logits=True)
+            log_prob, ent_pano, ent_offset, ent_distance, self.eval_flags = \
+                waypoint_dist.WaypointEvalFn.apply(
+                    logits, off_a, off_b, dist_a, dist_b, action_components["pano"],
+                    action_components["offset"], action_components["distance"], spec)
+            entropy = {"pano": ent_pano, "distance": ent_distance, "offset": ent_offset}
+            return self.critic(features), log_prob, entropy, rnn_states_out
         (heading_dist, off_a, off_b, dist_a, dist_b, features, rnn_states_out) = self.net(
             observations, rnn_states, prev_actions, masks)
         choice = action_components["pano"]

@@ -245,7 +245,9 @@ class WaypointPredictionNet(Net):
         emb = emb.reshape(b, n, *emb.shape[1:])
         return emb[:, : self._num_panos], emb[:, self._num_panos]
 
-    def forward(self, observations, rnn_states, prev_actions, masks):
+    def forward(self, observations, rnn_states, prev_actions, masks, raw_pano_logits=False):
+        """raw_pano_logits (internal, WaypointPolicy's one-launch evaluate_actions): the first result
+        is the tail's [B, P+1] logits themselves, not the Categorical over them."""
         for k in ("rgb", "depth", "instruction", "rgb_history", "depth_history", "angle_features"):
             assert k in observations
         P = self._num_panos
@@ -292,7 +294,7 @@ class WaypointPredictionNet(Net):
             ins, rgb.contiguous(), rgb_hist.contiguous(), dep.contiguous(), dep_hist.contiguous(),
             pa.contiguous(), observations["angle_features"].contiguous(), rnn_states.contiguous(),
             masks)
-        pano_stop = CustomFixedCategorical(logits=logits)
+        pano_stop = logits if raw_pano_logits else CustomFixedCategorical(logits=logits)
         if not wc.continuous_distance:
             d2 = None
         if not wc.continuous_offset:
