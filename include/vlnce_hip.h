@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 151 = this header */
+int vlnce_version(void); /* major*100 + minor; 152 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -1031,6 +1031,47 @@ int vlnce_waypoint_eval_bwd(const float* g_logp, const float* g_ent_pano, const 
                             const int32_t* flags, const vlnce_wp_part_grad* offset,
                             const vlnce_wp_part_grad* distance, int B, int P, float* d_logits,
                             vlnce_stream_t stream);
+
+/* The optimizer step of both reference trainers over a LIST of fp32 tensors (ABI 152): torch.optim.Adam
+ * (base_il_trainer.py:69-77, ddppo_waypoint_trainer.py:441) with torch.nn.utils.clip_grad_norm_ in front
+ * (WDDPPO.before_step), as two launches: vlnce_grad_sumsq (only when clipping), then vlnce_adam_step.
+ * No atomics, no grid-wide and no host synchronisation; every element is evaluated in fp64 and rounded
+ * once per store, and the reduction orders are fixed: two runs from the same state give the same bits.
+ *
+ * table (device, int64 words) is the stable half of the list, built by the caller once per parameter set:
+ *   n_tensors x { p, m, v (addresses of fp32 arrays), numel }, then n_chunks words, one per
+ *   vlnce_adam_chunk() elements of a tensor: tensor index << 32 | chunk index inside that tensor.
+ * A launch takes at most vlnce_adam_max_tensors() tensors; a longer list is split by the caller, each
+ * part with a table of its own.  The half that changes every step is read from HOST arrays at the call and
+ * travels by value in the kernel arguments (nothing is staged that a later call could overwrite):
+ *   grads[t]         the gradient's address; NULL skips the tensor entirely (torch: grad is None).  Read only.
+ *   step_size[t]     lr / (1 - beta1^t),  inv_bc2_sqrt[t] = 1 / sqrt(1 - beta2^t), t = the tensor's OWN step
+ *                    count after increment, computed in double as torch does
+ * Arrays may be views: 16-byte accesses are used where p, g, m, v of a chunk are all 16-byte aligned, a
+ * scalar path otherwise (decided per workgroup); either way element i of a chunk belongs to the same thread.
+ *
+ * vlnce_grad_sumsq: workgroup w of VLNCE_ADAM_PARTIALS adds the squares of the gradients in chunks w,
+ * w + VLNCE_ADAM_PARTIALS, ... in fp64 and stores partials[w] (accumulate = 0) or adds to it (accumulate != 0:
+ * the second and later parts of a split list), so the norm spans every part.
+ * vlnce_adam_step: with partials != NULL every workgroup adds the VLNCE_ADAM_PARTIALS values in one fixed
+ * order, total_norm = sqrt(sum), coef = min(1, max_norm / (total_norm + 1e-6)) (NaN stays NaN), and
+ * workgroup 0 stores (float) total_norm to norm_out (if not NULL); partials == NULL: coef = 1.  Then
+ *   g = coef * g;  g += weight_decay * p  (weight_decay != 0)
+ *   m += (g - m) (1 - beta1);  v = beta2 v + (1 - beta2) g g
+ *   p -= step_size * m / (sqrt(v) * inv_bc2_sqrt + eps)
+ * The gradients themselves stay unclipped: the one observable difference from clip_grad_norm_.
+ * A NULL table, grads or partials of vlnce_grad_sumsq, n_tensors outside 1..vlnce_adam_max_tensors() and
+ * n_chunks outside 0..2^31-1 are refused before anything is launched (vlnce_adam_supported says so). */
+enum { VLNCE_ADAM_PARTIALS = 512 };
+int vlnce_adam_supported(int n_tensors, long n_chunks);
+int vlnce_adam_max_tensors(void);
+int vlnce_adam_chunk(void);
+int vlnce_grad_sumsq(const int64_t* table, int n_tensors, long n_chunks, const float* const* grads,
+                     double* partials, int accumulate, vlnce_stream_t stream);
+int vlnce_adam_step(const int64_t* table, int n_tensors, long n_chunks, const float* const* grads,
+                    const double* step_size, const double* inv_bc2_sqrt, const double* partials,
+                    double max_norm, double beta1, double beta2, double eps, double weight_decay,
+                    float* norm_out, vlnce_stream_t stream);
 
 #ifdef __cplusplus
 }

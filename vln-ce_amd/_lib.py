@@ -22,6 +22,7 @@ _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
 _L = C.c_long
+_D = C.c_double
 
 
 def _buffer_format(explicit, *bufs):
@@ -136,6 +137,29 @@ class WpPartGrad(C.Structure):   # vlnce_wp_part_grad
     _fields_ = [("kind", _I), ("K", _I), ("weight", _F), ("d_first", _P), ("d_second", _P)]
 
 
+# ---- vlnce_grad_sumsq / vlnce_adam_step: the stable half of a tensor list
+ADAM_PARTIALS = 512   # VLNCE_ADAM_PARTIALS: doubles in the partials buffer
+
+
+class AdamTable:
+    """One launch's tensors: ps / ms / vs (kept alive here), the int64 words of the device table
+    (n x {p, m, v, numel}, then per chunk tensor << 32 | chunk index) and, for the HIP library, the
+    table on the device with the pinned buffer it was copied from."""
+
+    def __init__(self, ps, ms, vs, chunk):
+        self.ps, self.ms, self.vs = list(ps), list(ms), list(vs)
+        self.n_tensors = len(self.ps)
+        words, tail = [], []
+        for t, (p, m, v) in enumerate(zip(self.ps, self.ms, self.vs)):
+            assert m.numel() == p.numel() and v.numel() == p.numel()
+            words += [p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()]
+            tail += [(t << 32) | c for c in range((p.numel() + chunk - 1) // chunk)]
+        self.n_chunks = len(tail)
+        self.words = words + tail
+        self.key = tuple(words)
+        self.pinned = self.dev = None
+
+
 # ---- vlnce_waypoint_eval: one component (offset / distance) of the Waypoint action, as tensors
 WP_ABSENT, WP_CONTINUOUS, WP_DISCRETE = 0, 1, 2
 WP_FLAG_PANO = 1
@@ -215,6 +239,12 @@ _SIGNATURES = {
                                  _P]),
     "vlnce_waypoint_eval_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(WpPartGrad),
                                      C.POINTER(WpPartGrad), _I, _I, _P, _P]),
+    "vlnce_adam_supported": (_I, [_I, _L]),
+    "vlnce_adam_max_tensors": (_I, []),
+    "vlnce_adam_chunk": (_I, []),
+    "vlnce_grad_sumsq": (_I, [_P, _I, _L, C.POINTER(_P), _P, _I, _P]),
+    "vlnce_adam_step": (_I, [_P, _I, _L, C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), _P, _D, _D, _D, _D,
+                             _D, _P, _P]),
     "vlnce_space_to_depth2": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vlnce_frames_s2d": (_I, [C.POINTER(Frames), _P, _I, _I, _P, _P, _P]),
     "vlnce_frames_avgpool2": (_I, [C.POINTER(Frames), _P, _P]),
@@ -370,7 +400,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 151  # include/vlnce_hip.h
+    ABI = 152  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -857,6 +887,53 @@ class HipLib:
         self._check(self.dll.vlnce_waypoint_eval_bwd(
             *[_ptr(g) for g in grads], _ptr(pano), _ptr(saved), _ptr(flags), C.byref(descs[0]),
             C.byref(descs[1]), B, P, _ptr(d_logits), _stream()), "vlnce_waypoint_eval_bwd")
+
+    def adam_supported(self, n_tensors, n_chunks):
+        return bool(self.dll.vlnce_adam_supported(int(n_tensors), int(n_chunks)))
+
+    def adam_max_tensors(self):
+        return self.dll.vlnce_adam_max_tensors()
+
+    def adam_chunk(self):
+        return self.dll.vlnce_adam_chunk()
+
+    def adam_table(self, ps, ms, vs):
+        """the device table of one launch (<= adam_max_tensors() contiguous fp32 tensors on one GPU);
+        copied from a pinned buffer that lives as long as the table: no synchronisation"""
+        tab = AdamTable(ps, ms, vs, self.adam_chunk())
+        assert all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                   and t.device == tab.ps[0].device for t in tab.ps + tab.ms + tab.vs)
+        tab.pinned = torch.tensor(tab.words, dtype=torch.int64).pin_memory()
+        tab.dev = tab.pinned.to(tab.ps[0].device, non_blocking=True)
+        return tab
+
+    @staticmethod
+    def _grad_ptrs(tab, grads):
+        assert len(grads) == tab.n_tensors
+        # (the caller has checked dtype, device and contiguity: vlnce_amd.optim.Adam._collect)
+        assert all(g is None or g.numel() == p.numel() for g, p in zip(grads, tab.ps))
+        return (_P * tab.n_tensors)(*[None if g is None else g.data_ptr() for g in grads])
+
+    def grad_sumsq(self, tab, grads, partials, accumulate):
+        """partials [ADAM_PARTIALS] float64 (+)= the squares of the gradients present (None: skipped)"""
+        assert partials.dtype == torch.float64 and partials.numel() >= ADAM_PARTIALS
+        self._check(self.dll.vlnce_grad_sumsq(_ptr(tab.dev), tab.n_tensors, tab.n_chunks,
+                                              self._grad_ptrs(tab, grads), _ptr(partials),
+                                              int(bool(accumulate)), _stream()), "vlnce_grad_sumsq")
+
+    def adam_step(self, tab, grads, step_size, inv_bc2_sqrt, partials, max_norm, beta1, beta2, eps,
+                  weight_decay, norm_out):
+        """torch's Adam on every tensor of tab whose gradient is present; partials (or None) carries
+        the clip: coef = min(1, max_norm / (sqrt(sum partials) + 1e-6)), the norm stored to norm_out"""
+        n = tab.n_tensors
+        assert len(step_size) == n and len(inv_bc2_sqrt) == n
+        assert partials is None or (partials.dtype == torch.float64 and partials.numel() >= ADAM_PARTIALS)
+        assert norm_out is None or norm_out.dtype == torch.float32
+        self._check(self.dll.vlnce_adam_step(
+            _ptr(tab.dev), n, tab.n_chunks, self._grad_ptrs(tab, grads), (_D * n)(*step_size),
+            (_D * n)(*inv_bc2_sqrt), _ptr(partials), float(max_norm if partials is not None else 0.0),
+            float(beta1), float(beta2), float(eps), float(weight_decay), _ptr(norm_out), _stream()),
+            "vlnce_adam_step")
 
     def space_to_depth2(self, x, y, N, H, W, Cc, pad_lo, pad_hi, scale=None, shift=None):
         self._check(self.dll.vlnce_space_to_depth2(_ptr(x), _ptr(y), N, H, W, Cc, pad_lo, pad_hi,

@@ -48,7 +48,9 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // is not 16-byte aligned, and refuses every bad argument before it launches anything.
 // 151: vlnce_waypoint_eval / _bwd / _supported, vlnce_wp_part (WaypointPolicy.evaluate_actions' distribution
 // arithmetic: one launch forward, one backward, no host synchronisation); option "waypoint_dist".
-extern "C" int vlnce_version(void) { return 151; }
+// 152: vlnce_grad_sumsq / vlnce_adam_step / vlnce_adam_supported / _max_tensors / _chunk (clip_grad_norm_ + Adam
+// over a list of tensors in two launches; csrc/optim.hip).
+extern "C" int vlnce_version(void) { return 152; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)

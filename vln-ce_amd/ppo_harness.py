@@ -82,6 +82,13 @@ class PPOLossFn(torch.autograd.Function):
         return (*out, None, None, None, None, None, None)
 
 
+def _clips_itself(optimizer):
+    """vlnce_amd.optim.Adam(max_grad_norm=...) clips inside its own step (one norm launch)"""
+    from .optim import Adam
+
+    return isinstance(optimizer, Adam) and optimizer.max_grad_norm is not None
+
+
 def wddppo_minibatch_update(policy, optimizer, sample, cfg=PPOConfig(), *, step_grad=True,
                             clip_grads=True, grad_hook=None):
     (obs, h0, actions, prev_actions, value_preds, returns, masks, old_logp, adv) = sample
@@ -97,7 +104,7 @@ def wddppo_minibatch_update(policy, optimizer, sample, cfg=PPOConfig(), *, step_
     loss.backward()
     if grad_hook is not None:
         grad_hook()  # data-parallel gradient all-reduce (vlnce_amd.distributed)
-    if clip_grads and cfg.max_grad_norm is not None:
+    if clip_grads and cfg.max_grad_norm is not None and not (step_grad and _clips_itself(optimizer)):
         torch.nn.utils.clip_grad_norm_(policy.parameters(), cfg.max_grad_norm)
     if step_grad and optimizer is not None:
         optimizer.step()
