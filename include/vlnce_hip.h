@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 152 = this header */
+int vlnce_version(void); /* major*100 + minor; 153 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -1072,6 +1072,73 @@ int vlnce_adam_step(const int64_t* table, int n_tensors, long n_chunks, const fl
                     const double* step_size, const double* inv_bc2_sqrt, const double* partials,
                     double max_norm, double beta1, double beta2, double eps, double weight_decay,
                     float* norm_out, vlnce_stream_t stream);
+
+/* DD-PPO rollout storage (ABI 153): ActionDictRolloutStorage of
+ * vlnce_baselines/common/rollout_storage.py keeps its arenas [T+1, N, ...] on the device and moves rows
+ * with ~17 copy_ launches per simulator step (insert, :85-111), ~11 per after_update (:113-125) and a
+ * Python loop over environments with ~25 stack / view launches per minibatch (recurrent_generator,
+ * :154-276).  Here each of those is ONE launch over a TABLE of fields, the large sensors and the
+ * one-element rows alike.  The tables and the environment indices are HOST arrays, read during the call
+ * and carried in the kernel arguments: no upload, no allocation, no synchronisation.  Plain vector loads
+ * and stores only; all index arithmetic is 64-bit; element dtypes are the VLNCE_TRAJ_* codes.
+ *
+ * vlnce_rollout_copy: for every field f and row r < n_rows, E_f contiguous elements go from
+ * src_f + r*src_row_stride_f to dst_f + r*dst_row_stride_f (strides in elements of the own dtype; with
+ * n_rows == 1 they are not read), converted from src_dtype to dst_dtype.  Supported pairs, exactly:
+ * f32->f32, i64->i64, u8->u8 (a bool source is u8), i64->f32, u8->f32, and f32->i64 / f32->u8, which are
+ * defined only for finite values that the target represents exactly (masks, action indices).
+ * vlnce_rollout_copy_supported says so; any other pair is refused before anything is launched.  A row is
+ * dealt out in chunks of VLNCE_ROLLOUT_CHUNK elements, one workgroup each (a 7 MB row is spread over the
+ * machine); rows shorter than 256 elements are packed, one thread per element (a 1-element row costs one
+ * thread).  A field takes 16-byte accesses when both pointers and both row strides IN BYTES are 16-byte
+ * aligned and the dtypes are equal (a chunk's offset always is); otherwise, and for the tail of a row
+ * behind its last whole 16 bytes, one element per access.  Source and destination ranges of one call must
+ * not overlap (after_update with step == 0 is the caller's no-op).  At most VLNCE_ROLLOUT_MAX_FIELDS
+ * fields per call: the caller splits a longer table.
+ *
+ * vlnce_rollout_gather: the minibatch of recurrent_generator.  For every field and t < T_f (T_f = T, or 1
+ * for a field with once != 0: the initial hidden state, whose output is [n_envs, L, H]):
+ *   out_f[(t*out_N_f + j)*E_f + e] = arena_f[(t*N_f + envs[j])*E_f + e],   j < n_envs, e < E_f
+ * without conversion (elem_bytes 1 | 2 | 4 | 8).  Rows are time-major, t*n' + j.  At most
+ * VLNCE_ROLLOUT_MAX_ENVS environments per call: with more, the caller issues one call per 64, each with
+ * `out` advanced by 64*E_f elements and out_N_f the environment count of the WHOLE output (the output's
+ * time stride), which is why out_N is a field of its own and not n_envs.  Every envs[j] in [0, N_f).  The
+ * 16-byte path as above: arena and out 16-byte aligned and E_f*elem_bytes a multiple of 16.
+ *
+ * vlnce_ppo_advantages: WDDPPO.get_advantages (ddppo_alg.py:30-35) in one launch of ONE workgroup.
+ * returns / value_preds [T+1, N] (they carry the bootstrap row), adv [T, N].  d = returns - value_preds in
+ * fp32, one rounding, as torch; normalize == 0: adv = d, bit for bit.  Otherwise the mean and the unbiased
+ * standard deviation (divisor T*N - 1, as torch.std) of the fp32 d are taken in fp64 in a fixed order (two
+ * runs give the same bits), and adv = (d - mean) / (std + eps) is evaluated in fp64 and rounded once.
+ * T*N == 1 gives NaN, as torch does. */
+#define VLNCE_ROLLOUT_MAX_FIELDS 32
+#define VLNCE_ROLLOUT_MAX_ENVS 64
+#define VLNCE_ROLLOUT_CHUNK 4096
+typedef struct {
+  const void* src;      /* row 0 of the source                                           */
+  void* dst;            /* row 0 of the destination                                      */
+  long E;               /* elements per row, > 0                                         */
+  long src_row_stride;  /* in elements of src_dtype, >= 0                                */
+  long dst_row_stride;  /* in elements of dst_dtype, >= E                                */
+  int src_dtype;        /* VLNCE_TRAJ_F32 | _I64 | _U8                                   */
+  int dst_dtype;        /* VLNCE_TRAJ_F32 | _I64 | _U8                                   */
+} vlnce_rollout_field;
+typedef struct {
+  const void* arena;    /* [>= T_f, N, E]                                                */
+  void* out;            /* [T_f, out_N, E], at its first environment column of this call */
+  long E;               /* elements per (step, environment), > 0                         */
+  long N;               /* environments of the arena                                     */
+  long out_N;           /* environments of the whole output, >= n_envs                   */
+  int elem_bytes;       /* 1 | 2 | 4 | 8                                                 */
+  int once;             /* != 0: T_f = 1 whatever T                                      */
+} vlnce_rollout_gfield;
+int vlnce_rollout_copy_supported(int src_dtype, int dst_dtype);
+int vlnce_rollout_copy(const vlnce_rollout_field* fields, int n_fields, int n_rows,
+                       vlnce_stream_t stream);
+int vlnce_rollout_gather(const vlnce_rollout_gfield* fields, int n_fields, const int* envs, int n_envs,
+                         int T, vlnce_stream_t stream);
+int vlnce_ppo_advantages(const float* returns, const float* value_preds, float* adv, int T, int N,
+                         int normalize, float eps, vlnce_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -8,3 +8,4 @@ from .registry import baseline_registry, build_model  # noqa: F401
 from .seq2seq_policy import Seq2SeqPolicy  # noqa: F401
 from .cma_policy import CMAPolicy  # noqa: F401
 from .waypoint_policy import WaypointPolicy  # noqa: F401
+from .rollout_storage import ActionDictRolloutStorage  # noqa: F401

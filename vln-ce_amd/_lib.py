@@ -128,6 +128,25 @@ class TrajSensor(C.Structure):   # vlnce_traj_sensor
                 ("C", _I), ("P", _I), ("src_dtype", _I), ("dst_dtype", _I)]
 
 
+class RolloutField(C.Structure):   # vlnce_rollout_field
+    _fields_ = [("src", _P), ("dst", _P), ("E", _L), ("src_row_stride", _L), ("dst_row_stride", _L),
+                ("src_dtype", _I), ("dst_dtype", _I)]
+
+
+class RolloutGField(C.Structure):   # vlnce_rollout_gfield
+    _fields_ = [("arena", _P), ("out", _P), ("E", _L), ("N", _L), ("out_N", _L), ("elem_bytes", _I),
+                ("once", _I)]
+
+
+# ---- vlnce_rollout_copy / vlnce_rollout_gather: one field of a call, as tensors
+# src / dst: views that BEGIN at row 0 of the block (only their data pointer and dtype are read)
+RolloutCopyField = collections.namedtuple("RolloutCopyField", "src dst E src_row_stride dst_row_stride")
+# arena [>= T, N, ...] contiguous; out [T_f, out_N, ...] contiguous, written from environment column
+# `column` on; once: the field has one time step whatever T (the initial hidden state)
+RolloutGatherField = collections.namedtuple("RolloutGatherField", "arena out E N out_N column once")
+ROLLOUT_MAX_FIELDS, ROLLOUT_MAX_ENVS = 32, 64   # VLNCE_ROLLOUT_MAX_FIELDS / _MAX_ENVS
+
+
 class WpPart(C.Structure):   # vlnce_wp_part
     _fields_ = [("kind", _I), ("K", _I), ("lo", _F), ("hi", _F), ("weight", _F), ("first", _P),
                 ("second", _P), ("element", _P)]
@@ -245,6 +264,10 @@ _SIGNATURES = {
     "vlnce_grad_sumsq": (_I, [_P, _I, _L, C.POINTER(_P), _P, _I, _P]),
     "vlnce_adam_step": (_I, [_P, _I, _L, C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), _P, _D, _D, _D, _D,
                              _D, _P, _P]),
+    "vlnce_rollout_copy_supported": (_I, [_I, _I]),
+    "vlnce_rollout_copy": (_I, [C.POINTER(RolloutField), _I, _I, _P]),
+    "vlnce_rollout_gather": (_I, [C.POINTER(RolloutGField), _I, C.POINTER(_I), _I, _I, _P]),
+    "vlnce_ppo_advantages": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "vlnce_space_to_depth2": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vlnce_frames_s2d": (_I, [C.POINTER(Frames), _P, _I, _I, _P, _P, _P]),
     "vlnce_frames_avgpool2": (_I, [C.POINTER(Frames), _P, _P]),
@@ -400,7 +423,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 152  # include/vlnce_hip.h
+    ABI = 153  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -934,6 +957,51 @@ class HipLib:
             (_D * n)(*inv_bc2_sqrt), _ptr(partials), float(max_norm if partials is not None else 0.0),
             float(beta1), float(beta2), float(eps), float(weight_decay), _ptr(norm_out), _stream()),
             "vlnce_adam_step")
+
+    # ---- DD-PPO rollout storage (csrc/rollout.hip)
+    _ROLLOUT_DTYPES = {**_TRAJ, torch.bool: _TRAJ[torch.uint8]}   # a bool source is u8
+
+    def rollout_copy_supported(self, src_dtype, dst_dtype):
+        """whether vlnce_rollout_copy converts this pair of torch dtypes"""
+        s, d = self._ROLLOUT_DTYPES.get(src_dtype), self._TRAJ.get(dst_dtype)
+        return s is not None and d is not None and bool(self.dll.vlnce_rollout_copy_supported(s, d))
+
+    def rollout_copy(self, fields, n_rows):
+        """one launch: for every RolloutCopyField and r < n_rows, E elements from src + r *
+        src_row_stride to dst + r * dst_row_stride (strides in elements), converted to dst's dtype.
+        At most ROLLOUT_MAX_FIELDS fields: the caller splits a longer table."""
+        codes = self._ROLLOUT_DTYPES
+        arr = (RolloutField * len(fields))(*[
+            RolloutField(_ptr(f.src), _ptr(f.dst), f.E, f.src_row_stride, f.dst_row_stride,
+                         codes[f.src.dtype], codes[f.dst.dtype]) for f in fields])
+        self._check(self.dll.vlnce_rollout_copy(arr, len(fields), int(n_rows), _stream()),
+                    "vlnce_rollout_copy")
+
+    def rollout_gather(self, fields, envs, T):
+        """one launch: for every RolloutGatherField, t < T (t < 1 where once) and j < len(envs),
+        out[t, column + j] = arena[t, envs[j]].  envs: a host sequence of at most ROLLOUT_MAX_ENVS
+        ints, carried in the launch's arguments."""
+        arr = (RolloutGField * len(fields))()
+        for a, f in zip(arr, fields):
+            assert f.arena.dtype == f.out.dtype and f.arena.is_contiguous() and f.out.is_contiguous()
+            es = f.arena.element_size()
+            a.arena, a.out = _ptr(f.arena), _ptr(f.out) + f.column * f.E * es
+            a.E, a.N, a.out_N, a.elem_bytes, a.once = f.E, f.N, f.out_N, es, int(bool(f.once))
+            rows = 1 if f.once else T
+            assert f.arena.numel() >= rows * f.N * f.E and f.out.numel() == rows * f.out_N * f.E
+            assert 0 <= f.column and f.column + len(envs) <= f.out_N
+        ev = (_I * len(envs))(*[int(e) for e in envs])
+        self._check(self.dll.vlnce_rollout_gather(arr, len(fields), ev, len(envs), int(T), _stream()),
+                    "vlnce_rollout_gather")
+
+    def ppo_advantages(self, returns, value_preds, adv, T, N, normalize, eps):
+        """WDDPPO.get_advantages in one launch: returns / value_preds [>= T+1, N] fp32 contiguous
+        (rows < T are read), adv [T, N] fp32"""
+        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (returns, value_preds, adv))
+        assert returns.numel() >= T * N and value_preds.numel() >= T * N and adv.numel() == T * N
+        self._check(self.dll.vlnce_ppo_advantages(_ptr(returns), _ptr(value_preds), _ptr(adv), int(T),
+                                                  int(N), int(bool(normalize)), float(eps), _stream()),
+                    "vlnce_ppo_advantages")
 
     def space_to_depth2(self, x, y, N, H, W, Cc, pad_lo, pad_hi, scale=None, shift=None):
         self._check(self.dll.vlnce_space_to_depth2(_ptr(x), _ptr(y), N, H, W, Cc, pad_lo, pad_hi,

@@ -50,7 +50,9 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // arithmetic: one launch forward, one backward, no host synchronisation); option "waypoint_dist".
 // 152: vlnce_grad_sumsq / vlnce_adam_step / vlnce_adam_supported / _max_tensors / _chunk (clip_grad_norm_ + Adam
 // over a list of tensors in two launches; csrc/optim.hip).
-extern "C" int vlnce_version(void) { return 152; }
+// 153: vlnce_rollout_copy / _copy_supported / _gather, vlnce_ppo_advantages (the DD-PPO rollout storage's insert,
+// after_update, minibatch gather and advantages, one launch each; csrc/rollout.hip).
+extern "C" int vlnce_version(void) { return 153; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)

@@ -168,6 +168,10 @@ __global__ __launch_bounds__(256) void ppo_returns_kernel(const float* __restric
                                                           const float* __restrict__ next_value,
                                                           float* __restrict__ returns, int T, int N,
                                                           float gamma, float gamma_tau, int use_gae) {
+  // every product and sum rounds on its own, as the reference's tensor arithmetic does: a fused
+  // gamma_tau * m1 * gae + delta differs from it in the last bit, and the rollout storage's goldens
+  // hold `returns` to the reference bit for bit
+#pragma clang fp contract(off)
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   if (use_gae) {

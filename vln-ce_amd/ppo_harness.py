@@ -110,3 +110,26 @@ def wddppo_minibatch_update(policy, optimizer, sample, cfg=PPOConfig(), *, step_
         optimizer.step()
     # (value_loss, action_loss, entropy_loss, pano / offset / distance entropy) as WDDPPO.update sums
     return tuple(stats[1:7].unbind(0))
+
+
+def wddppo_update(policy, optimizer, rollouts, cfg=PPOConfig(), *, ppo_epoch=2, num_mini_batch=4,
+                  use_normalized_advantage=False, grad_hook=None):
+    """WDDPPO.update (ddppo_alg.py:37-149) over any storage that has `recurrent_generator` and the
+    arenas (vlnce_amd.ActionDictRolloutStorage, or the reference's own class): `ppo_epoch` passes of
+    `num_mini_batch` minibatches, each through wddppo_minibatch_update.  The six statistics
+    accumulate on the device and are read back ONCE, at the end (the reference calls .item() six
+    times per minibatch); returns their means over the ppo_epoch * num_mini_batch updates:
+    (value_loss, action_loss, entropy_loss, pano / offset / distance entropy)."""
+    if hasattr(rollouts, "get_advantages"):
+        advantages = rollouts.get_advantages(use_normalized_advantage)
+    else:
+        advantages = normalized_advantages(rollouts.returns, rollouts.value_preds,
+                                           use_normalized_advantage)
+    totals = None
+    for _e in range(ppo_epoch):
+        for sample in rollouts.recurrent_generator(advantages, num_mini_batch):
+            stats = torch.stack(wddppo_minibatch_update(policy, optimizer, sample, cfg,
+                                                        grad_hook=grad_hook))
+            totals = stats if totals is None else totals + stats
+    num_updates = ppo_epoch * num_mini_batch
+    return tuple(v / num_updates for v in totals.tolist())
