@@ -9,7 +9,7 @@ while [ $# -ge 2 ]; do
   d=build/variants/obj_$name; mkdir -p $d
   for f in vln-ce_amd/csrc/*.hip vln-ce_amd/csrc/*.cpp; do
     b=$(basename ${f%.*})
-    case $b in igemm|conv_p3|conv_u3|conv_s3) rebuild=1 ;; *) rebuild=0 ;; esac   # the files that read -D flags
+    case $b in conv_x3|conv_p3|conv_u3|conv_s3) rebuild=1 ;; *) rebuild=0 ;; esac   # the files that read -D flags
     if [ $rebuild = 1 ] || [ ! -f build/$b.o ]; then
       /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $flags -c $f -o $d/$b.o &
     else

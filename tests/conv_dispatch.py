@@ -1,6 +1,6 @@
 """The convolution dispatch of vlnce_conv2d_fwd written out a second time, in Python, from reading
-vlnce_conv2d_fwd (igemm.hip), p3_try_launch_ (conv_p3.hip), m3_try_launch (conv_m3.hip) and x3_plan /
-choose_splitk (igemm.hip): which kernel INSTANCE a launch must land on, as the ConvKernel tuple that
+vlnce_conv2d_fwd / choose_splitk (igemm.hip), p3_try_launch_ (conv_p3.hip), m3_try_launch (conv_m3.hip)
+and x3_plan (conv_x3.hip): which kernel INSTANCE a launch must land on, as the ConvKernel tuple that
 HipLib.conv2d_last_kernel() decodes.  The GPU tests compare the two after every launch, so a changed
 eligibility rule, a forced tile that silently does not fit or an instance nothing reaches any more
 fails a test instead of moving a case to another kernel unnoticed.

@@ -1,5 +1,5 @@
 """The dispatch of vlnce_gemm written out a second time, in Python, from reading vlnce_gemm,
-choose_splitk, choose_tile, buf_ok and dispatch_tiles / dispatch_small (csrc/igemm.hip): which
+choose_splitk, choose_tile and dispatch_tiles / dispatch_small (csrc/igemm.hip), buf_ok (igemm_shared.h): which
 igemm_kernel instance a call must land on and what runs around it, as the GemmKernel tuple that
 HipLib.gemm_last_kernel() decodes.  The GPU tests compare the two after every launch, so a changed
 split threshold, a changed eligibility rule of the buffer loaders or a changed alignment test fails a

@@ -228,8 +228,10 @@ def run_instance(hip, inst, fmt, signed, prologue, hot=None):
                    w_split=ops.split_weights(t["w"], pf), w_frag=ops.pack_weights(t["w"], pf),
                    options=dict(inst.opts, conv_math=fmt), **t)
     got = hip.conv2d_last_kernel()
+    path = hip.conv2d_last_path()
     torch.cuda.synchronize()
     assert got == inst.kernel._replace(fmt=fmt), (inst.shape, inst.opts, "ran on", got)
+    assert path == ("f32", "x3", "p3", "m3").index(got.family), (inst.shape, inst.opts, path, got)
     return y.reshape(-1, Cout), op
 
 

@@ -1,6 +1,6 @@
 // conv_p3_kernel: fp32 convolution on the bf16 matrix pipe with a PATCH-RESIDENT A operand.
 //
-// Same arithmetic as conv_x3_kernel (igemm.hip): every fp32 operand is split exactly into three
+// Same arithmetic as conv_x3_kernel (conv_x3.hip): every fp32 operand is split exactly into three
 // bf16 planes and a product is the six plane products of order <= 2^-16 on
 // v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- here with a round-to-nearest split
 // (v_cvt_pk_bf16_f32), so the dropped cross terms are <= 2^-26 relative.

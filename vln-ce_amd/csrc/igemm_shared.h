@@ -474,10 +474,23 @@ static inline int x3_lds_max() {
 // launch hands over (vlnce_prologue.w_format -> IgemmParams::math: MATH_BF16X6 or MATH_F16X3).
 static inline int conv_math() { return vlnce_opt(VLNCE_OPT_CONV_MATH) != 0; }
 
+// buffer-descriptor hot path: channels-last im2col / row-major A with Cin % 32 == 0, at most
+// 32 filter taps, [N,K] weights, operands below 2 GiB
+inline bool buf_ok(const IgemmParams& p) {
+  const bool off = vlnce_opt(VLNCE_OPT_IGEMM_NOBUF) != 0;
+  const long bias = ((long)p.pad * p.W + p.pad) * p.lda * 4;
+  return !off && (p.Cin % 32 == 0) && (p.K % 32 == 0) && (p.lda % 4 == 0) && (p.ldb % 4 == 0) &&
+         p.KH * p.KW <= 32 && p.a_bytes + bias < 0x7fffffffL && p.b_bytes < 0x7fffffffL;
+}
+inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
 // conv_p3.hip: the router of the patch-resident plane convolutions (conv_p3 / u3 / s3 kernels).
 // Returns -1 when the problem is not one they cover (the caller falls through to conv_x3_kernel /
 // igemm_kernel), else a C-ABI status.
 int p3_try_launch(const IgemmParams& p, hipStream_t stream);
+// conv_x3.hip: conv_x3_kernel (dual: the two-input block-end prologue).  -1 when its planner
+// declines (the caller falls through to igemm_kernel), else a C-ABI status.
+int x3_try_launch(const IgemmParams& p, bool dual, hipStream_t stream);
 // The kernels the router hands eligible problems to (it has tested eligibility):
 // conv_u3.hip: bm = 64 / 128 tile rows, dual_kind = DUAL of conv_u3_kernel, waves = 8, or 4 (64-row tiles)
 constexpr int U3_MAX_CIN = 4096;   // conv_u3_kernel: input channels whose prologue vectors fit its LDS

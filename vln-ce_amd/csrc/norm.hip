@@ -138,6 +138,43 @@ __global__ __launch_bounds__(256) void bn_coarsen_kernel(const float* __restrict
   }
 }
 
+// {sum x, sum x^2} per channel (fp64, added by the convolution's workgroups) -> the pending
+// normalisation and the running statistics; leaves the sums zero for the next launch.  One
+// workgroup per 256 channels: ~2 us + a launch boundary behind the convolution instead of
+// finalize (+ coarsen) over thousands of tile moments.
+__global__ __launch_bounds__(256) void bn_sums_finalize_kernel(
+    double* __restrict__ acc, int M, int N, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float eps, float momentum, float* running_mean,
+    float* running_var, float* scale_out, float* shift_out, float* mean_out, float* rstd_out) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= N) return;
+  double S = 0.0, Q = 0.0;
+#pragma unroll
+  for (int k = 0; k < VLNCE_BN_SHARDS; ++k) {
+    double* q = acc + ((long)k * N + c) * 2;
+    S += q[0];
+    Q += q[1];
+    q[0] = 0.0;
+    q[1] = 0.0;
+  }
+  const double mean = S / (double)M;
+  double m2 = Q - S * mean;           // sum (x - mean)^2
+  if (m2 < 0.0) m2 = 0.0;
+  const double var = m2 / (double)M;  // biased, used for normalisation
+  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+  const float g = gamma ? gamma[c] : 1.f;
+  const float sc = g * rstd;
+  scale_out[c] = sc;
+  if (shift_out) shift_out[c] = (beta ? beta[c] : 0.f) - (float)mean * sc;
+  if (mean_out) mean_out[c] = (float)mean;
+  if (rstd_out) rstd_out[c] = rstd;
+  if (running_mean) {
+    const double unbiased = M > 1 ? m2 / (double)(M - 1) : var;
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+  }
+}
+
 // ---------------------------------------------------------------- scale/shift/act apply
 template <bool VEC>
 __global__ __launch_bounds__(256) void scale_shift_act_kernel(
@@ -357,6 +394,20 @@ extern "C" int vlnce_bn_finalize(const float* stat_partial, int tiles_m, int til
                        stat_partial, tiles_m, tile_rows, M, C, gamma, beta, eps, momentum,
                        running_mean, running_var, scale_out, shift_out, mean_out, rstd_out);
   VLNCE_CHECK_LAUNCH("bn_finalize");
+  return 0;
+}
+
+extern "C" int vlnce_bn_finalize_sums(double* acc, int M, int C, const float* gamma, const float* beta,
+                                      float eps, float momentum, float* running_mean,
+                                      float* running_var, float* scale_out, float* shift_out,
+                                      float* mean_out, float* rstd_out, vlnce_stream_t stream) {
+  VLNCE_CHECK_ARG(acc && scale_out && M > 0 && C > 0, "bn_finalize_sums: bad argument");
+  VLNCE_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr),
+                  "bn_finalize_sums: running stats must come together");
+  hipLaunchKernelGGL(bn_sums_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), acc, M, C, gamma, beta, eps, momentum,
+                     running_mean, running_var, scale_out, shift_out, mean_out, rstd_out);
+  VLNCE_CHECK_LAUNCH("bn_finalize_sums");
   return 0;
 }
 

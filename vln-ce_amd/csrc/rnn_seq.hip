@@ -94,7 +94,7 @@ __device__ __forceinline__ float tanh_fast(float x) {
 
 // fp32 recurrent product on the bf16 matrix pipe: both operands are split exactly into three
 // bf16 planes (truncation: 8 + 8 + 8 mantissa bits) and multiplied as the six plane products of
-// order <= 2^-16, fp32 accumulate -- the arithmetic of conv_x3_kernel (igemm.hip).  One
+// order <= 2^-16, fp32 accumulate -- the arithmetic of conv_x3_kernel (conv_x3.hip).  One
 // v_mfma_f32_16x16x32_bf16 (16 cycles) covers 32 k-values where v_mfma_f32_16x16x4_f32
 // (32 cycles) covers 4: 2.7x less matrix-pipe time per step, on the step's critical path.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -5,6 +5,7 @@
 // -- ~900 launches of ~4 us each per step for the two ResNet-50 trunks, more GPU time than the
 // bytes they move (profiles/r06_m_trainable_step_kernels.txt).  A job table on the device names
 // every output; a work item is eight consecutive input channels of one (filter, tap).
+// Also here: the plane split of one weight tensor on its own (vlnce_conv2d_split_weights).
 #include "igemm_shared.h"
 
 using namespace vlnce_detail;
@@ -90,7 +91,36 @@ __global__ __launch_bounds__(256) void weight_prep_kernel(const vlnce_weight_job
   }
 }
 
+// w[i] -> planes[q][i], q = 0..2: the exact three-way (round-to-nearest) bf16 split of
+// conv_x3_kernel's B operand
+template <int MATH>
+__global__ __launch_bounds__(256) void split_weights_kernel(const float* __restrict__ w,
+                                                            unsigned short* __restrict__ planes,
+                                                            long count) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < count; i += gridDim.x * 256L) {
+    unsigned short o[3];   // MATH_BF16X6: w == plane0 + plane1 + plane2 exactly
+    split_weight<MATH>(w[i], o);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) planes[q * count + i] = o[q];
+  }
+}
+
 }  // namespace
+
+extern "C" int vlnce_conv2d_split_weights(const float* w, void* planes, long count, int format,
+                                          vlnce_stream_t stream) {
+  VLNCE_CHECK_ARG(w && planes && count > 0, "conv2d_split_weights: bad argument");
+  VLNCE_CHECK_ARG(format == MATH_BF16X6 || format == MATH_F16X3,
+                  "conv2d_split_weights: format must be 1 (three bf16 planes) or 2 (fp16 planes)");
+  const long blocks = (count + 255) / 256;
+  hipLaunchKernelGGL(format == MATH_F16X3 ? split_weights_kernel<MATH_F16X3>
+                                          : split_weights_kernel<MATH_BF16X6>,
+                     dim3((unsigned)(blocks > 4096 ? 4096 : blocks)),
+                     dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w,
+                     reinterpret_cast<unsigned short*>(planes), count);
+  VLNCE_CHECK_LAUNCH("conv2d_split_weights");
+  return 0;
+}
 
 extern "C" long vlnce_weight_job_items(const vlnce_weight_job* job) {
   if (!job || job->Cout <= 0 || job->Cin <= 0 || job->T <= 0) return -1;
