@@ -11,6 +11,7 @@ one process on one MI355X.
      H = 512, beside the GRU rollout at the same shapes.
 
     python scripts/lstm_rollout_ab.py [--steps 40] [--warmup 6] [--reps 30]
+    python scripts/lstm_rollout_ab.py --kernels-only    # part 2 alone (e.g. once per VLNCE_HIP_LIB)
 """
 import argparse
 import os
@@ -174,12 +175,14 @@ def main():
     ap.add_argument("--steps", type=int, default=40, help="timed update steps per arm (>= 30)")
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--kernels-only", action="store_true", help="only the two rollout launches alone")
     a = ap.parse_args()
     assert a.steps >= 30, "the medians are of at least 30 steps per arm"
     dev = torch.device("cuda:0")
     lib = ops.L()
-    update_ab(a, dev, lib, graphs=True)
-    update_ab(a, dev, lib, graphs=False)
+    if not a.kernels_only:
+        update_ab(a, dev, lib, graphs=True)
+        update_ab(a, dev, lib, graphs=False)
     kernels(a, dev, lib)
 
 

@@ -1,5 +1,5 @@
 """GPU tier: the LSTM state-encoder rollout as ONE launch forward and ONE backward
-(vlnce_lstm_rollout_fwd / _bwd, csrc/gru_rollout.hip) -- the kernels against T step launches, the
+(vlnce_lstm_rollout_fwd / _bwd, csrc/rnn_rollout.hip) -- the kernels against T step launches, the
 autograd node and a CMA policy with STATE_ENCODER.rnn_type = LSTM taking that path, the shapes that
 must not take it, and a captured graph of it."""
 import pytest

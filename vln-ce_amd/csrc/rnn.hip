@@ -1,10 +1,10 @@
 // Recurrent-cell pointwise stages (GRU / LSTM, torch gate order) and small
 // row utilities.  The GEMM halves (x W_ih^T, h W_hh^T) run on the MFMA kernel.
+// The cell arithmetic itself is rnn_cell.h's.
 #include "common.h"
+#include "rnn_cell.h"
 
 namespace {
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
 __global__ __launch_bounds__(256) void gru_gates_fwd_kernel(
     const float* __restrict__ gi, const float* __restrict__ gh, const float* __restrict__ h_prev,
@@ -19,16 +19,15 @@ __global__ __launch_bounds__(256) void gru_gates_fwd_kernel(
     const float* ghb = gh + b * 3 * H;
     float hp = h_prev[i];
     if (mask) hp *= (float)mask[b];
-    const float r = sigm(gib[j] + ghb[j]);
-    const float z = sigm(gib[H + j] + ghb[H + j]);
     const float hn = ghb[2 * H + j];
-    const float n = tanhf(gib[2 * H + j] + r * hn);
-    h_out[i] = (1.f - z) * n + z * hp;
+    const rnn_cell::GruFwd c =
+        rnn_cell::gru_fwd(hp, gib[j], ghb[j], gib[H + j], ghb[H + j], gib[2 * H + j], hn);
+    h_out[i] = c.h;
     if (gates_out) {
       float* g = gates_out + b * 3 * H;
-      g[j] = r;
-      g[H + j] = z;
-      g[2 * H + j] = n;
+      g[j] = c.r;
+      g[H + j] = c.z;
+      g[2 * H + j] = c.n;
     }
     if (hn_out) hn_out[i] = hn;
   }
@@ -48,20 +47,15 @@ __global__ __launch_bounds__(256) void gru_gates_bwd_kernel(
     const float mk = mask ? (float)mask[b] : 1.f;
     const float hp = h_prev[i] * mk;
     const float d = dh_out[i];
-    const float dn = d * (1.f - z);
-    const float dz = d * (hp - n);
-    const float dnp = dn * (1.f - n * n);
-    const float dr = dnp * hn[i];
-    const float drp = dr * r * (1.f - r);
-    const float dzp = dz * z * (1.f - z);
+    const rnn_cell::GruBwd q = rnn_cell::gru_bwd(d, r, z, n, hp, hn[i]);
     float* a = dgi + b * 3 * H;
     float* c = dgh + b * 3 * H;
-    a[j] = drp;
-    a[H + j] = dzp;
-    a[2 * H + j] = dnp;
-    c[j] = drp;
-    c[H + j] = dzp;
-    c[2 * H + j] = dnp * r;
+    a[j] = q.dr;
+    a[H + j] = q.dz;
+    a[2 * H + j] = q.dn;
+    c[j] = q.dr;
+    c[H + j] = q.dz;
+    c[2 * H + j] = q.dgh_n;
     dh_prev[i] = d * z * mk;
   }
 }
@@ -79,19 +73,17 @@ __global__ __launch_bounds__(256) void lstm_gates_fwd_kernel(
     const float* c = gh + b * 4 * H;
     float cp = c_prev[i];
     if (mask) cp *= (float)mask[b];
-    const float ig = sigm(a[j] + c[j]);
-    const float fg = sigm(a[H + j] + c[H + j]);
-    const float gg = tanhf(a[2 * H + j] + c[2 * H + j]);
-    const float og = sigm(a[3 * H + j] + c[3 * H + j]);
-    const float cn = fg * cp + ig * gg;
-    c_out[i] = cn;
-    h_out[i] = og * tanhf(cn);
+    const rnn_cell::LstmFwd q = rnn_cell::lstm_fwd(cp, a[j] + c[j], a[H + j] + c[H + j],
+                                                   a[2 * H + j] + c[2 * H + j],
+                                                   a[3 * H + j] + c[3 * H + j]);
+    c_out[i] = q.c;
+    h_out[i] = q.h;
     if (gates_out) {
       float* g = gates_out + b * 4 * H;
-      g[j] = ig;
-      g[H + j] = fg;
-      g[2 * H + j] = gg;
-      g[3 * H + j] = og;
+      g[j] = q.i;
+      g[H + j] = q.f;
+      g[2 * H + j] = q.g;
+      g[3 * H + j] = q.o;
     }
   }
 }
@@ -110,15 +102,16 @@ __global__ __launch_bounds__(256) void lstm_gates_bwd_kernel(
     const float ig = g[j], fg = g[H + j], gg = g[2 * H + j], og = g[3 * H + j];
     const float mk = mask ? (float)mask[b] : 1.f;
     const float cp = c_prev[i] * mk;
-    const float tc = tanhf(c_out[i]);
+    const float ct = c_out[i];
     const float dh = dh_out ? dh_out[i] : 0.f;
-    float dc = (dc_out ? dc_out[i] : 0.f) + dh * og * (1.f - tc * tc);
+    const rnn_cell::LstmBwd q =
+        rnn_cell::lstm_bwd(dh, ig, fg, gg, og, cp, ct, dc_out ? dc_out[i] : 0.f);
     float* d = dgates + b * 4 * H;
-    d[j] = dc * gg * ig * (1.f - ig);
-    d[H + j] = dc * cp * fg * (1.f - fg);
-    d[2 * H + j] = dc * ig * (1.f - gg * gg);
-    d[3 * H + j] = dh * tc * og * (1.f - og);
-    dc_prev[i] = dc * fg * mk;
+    d[j] = q.di;
+    d[H + j] = q.df;
+    d[2 * H + j] = q.dg;
+    d[3 * H + j] = q.do_;
+    dc_prev[i] = q.dcp * mk;
   }
 }
 
@@ -302,27 +295,22 @@ __global__ __launch_bounds__(256) void rnn_step_fwd_kernel(
     float* gs = gates_out + (long)n * G * H;
     if constexpr (LSTM) {
       const float cp = c_prev[o] * (mask ? (float)mask[n] : 1.f);
-      const float ig = sigm(gib[j] + gh[0]);
-      const float fg = sigm(gib[H + j] + gh[1]);
-      const float gg = tanhf(gib[2 * H + j] + gh[2]);
-      const float og = sigm(gib[3 * H + j] + gh[3]);
-      const float cn = fg * cp + ig * gg;
-      aux_out[o] = cn;
-      h_out[o] = og * tanhf(cn);
-      gs[j] = ig;
-      gs[H + j] = fg;
-      gs[2 * H + j] = gg;
-      gs[3 * H + j] = og;
+      const rnn_cell::LstmFwd q = rnn_cell::lstm_fwd(cp, gib[j] + gh[0], gib[H + j] + gh[1],
+                                                     gib[2 * H + j] + gh[2], gib[3 * H + j] + gh[3]);
+      aux_out[o] = q.c;
+      h_out[o] = q.h;
+      gs[j] = q.i;
+      gs[H + j] = q.f;
+      gs[2 * H + j] = q.g;
+      gs[3 * H + j] = q.o;
     } else {
-      const float hp = Xs[n * Hp + j];
-      const float r = sigm(gib[j] + gh[0]);
-      const float z = sigm(gib[H + j] + gh[1]);
-      const float n_ = tanhf(gib[2 * H + j] + r * gh[2]);
-      h_out[o] = (1.f - z) * n_ + z * hp;
+      const rnn_cell::GruFwd q = rnn_cell::gru_fwd(Xs[n * Hp + j], gib[j], gh[0], gib[H + j], gh[1],
+                                                   gib[2 * H + j], gh[2]);
+      h_out[o] = q.h;
       aux_out[o] = gh[2];
-      gs[j] = r;
-      gs[H + j] = z;
-      gs[2 * H + j] = n_;
+      gs[j] = q.r;
+      gs[H + j] = q.z;
+      gs[2 * H + j] = q.n;
     }
   }
 }
@@ -347,29 +335,23 @@ __global__ __launch_bounds__(256) void rnn_step_bwd_gates_kernel(
       const float ig = g[j], fg = g[H + j], gg = g[2 * H + j], og = g[3 * H + j];
       const float mk = mask ? (float)mask[n] : 1.f;
       const float cp = c_prev[i] * mk;
-      const float tc = tanhf(aux[i]);
-      const float dcc = dc[i] + d * og * (1.f - tc * tc);
-      a[j] = dcc * gg * ig * (1.f - ig);
-      a[H + j] = dcc * cp * fg * (1.f - fg);
-      a[2 * H + j] = dcc * ig * (1.f - gg * gg);
-      a[3 * H + j] = d * tc * og * (1.f - og);
-      dc_prev[i] = dcc * fg * mk;
+      const rnn_cell::LstmBwd q = rnn_cell::lstm_bwd(d, ig, fg, gg, og, cp, aux[i], dc[i]);
+      a[j] = q.di;
+      a[H + j] = q.df;
+      a[2 * H + j] = q.dg;
+      a[3 * H + j] = q.do_;
+      dc_prev[i] = q.dcp * mk;
       acc0[i] = 0.f;
     } else {
       const float r = g[j], z = g[H + j], nn = g[2 * H + j];
-      const float dn = d * (1.f - z);
-      const float dz = d * (hp[i] - nn);
-      const float dnp = dn * (1.f - nn * nn);
-      const float dr = dnp * aux[i];
-      const float drp = dr * r * (1.f - r);
-      const float dzp = dz * z * (1.f - z);
-      a[j] = drp;
-      a[H + j] = dzp;
-      a[2 * H + j] = dnp;
+      const rnn_cell::GruBwd q = rnn_cell::gru_bwd(d, r, z, nn, hp[i], aux[i]);
+      a[j] = q.dr;
+      a[H + j] = q.dz;
+      a[2 * H + j] = q.dn;
       float* c = dgh + n * G * H;
-      c[j] = drp;
-      c[H + j] = dzp;
-      c[2 * H + j] = dnp * r;
+      c[j] = q.dr;
+      c[H + j] = q.dz;
+      c[2 * H + j] = q.dgh_n;
       acc0[i] = d * z;
     }
   }

@@ -1050,7 +1050,7 @@ class MaskedRNNSeqFn(Function):
     t before step t).  A T-step rollout of N episodes -- the cached-feature DAgger batch
     (dagger_trainer.py:39-114) or a DD-PPO minibatch (rollout_storage.py:154-276) -- costs
     ONE launch forward and ONE backward for a GRU or an LSTM over N <= 16 episodes
-    (gru_rollout.hip: the recurrent weights stay in the registers of H/16 resident workgroups,
+    (rnn_rollout.hip: the recurrent weights stay in the registers of H/16 resident workgroups,
     one device-scope exchange per step; an LSTM's cell state never leaves its thread's register)
     where the library reports the shape supported on the device; otherwise 1-3 launches per step forward (mask, h W_hh^T, gates) and 2-3
     backward (gates', dgates W_hh, mask + skip add) instead of one autograd cell per step.  The
@@ -1079,7 +1079,7 @@ class MaskedRNNSeqFn(Function):
         # (a library without the LSTM entry points, e.g. the CPU simulator, steps an LSTM)
         supported = getattr(lib, "lstm_rollout_supported", None) if lstm else lib.gru_rollout_supported
         ctx.rollout = T > 1 and supported is not None and bool(supported(N, H))
-        if ctx.rollout:  # the whole recurrence in ONE launch (gru_rollout.hip)
+        if ctx.rollout:  # the whole recurrence in ONE launch (rnn_rollout.hip)
             ctx.lstm, ctx.dims = lstm, (T, N, H, GH)
             if lstm:
                 ws = _rollout_workspace(dev, lib.lstm_rollout_workspace_bytes(N, H))
