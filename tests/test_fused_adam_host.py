@@ -52,7 +52,7 @@ class AdamSim(hostsim.HostSim):
         """contract of vlnce_adam_step, in fp32: coef = min(1, max_norm / (norm + 1e-6)) with the
         norm over every launch's gradients; then torch's Adam on each tensor whose gradient is
         present, step_size = lr / (1 - beta1^t), inv_bc2_sqrt = 1 / sqrt(1 - beta2^t) per tensor.
-        The gradients are left as they are."""
+        The gradients are left as they are, and so is every tensor's `_version`."""
         assert len(grads) == len(step_size) == len(inv_bc2_sqrt) == tab.n_tensors
         coef = None
         if partials is not None:
@@ -70,7 +70,9 @@ class AdamSim(hostsim.HostSim):
                 g = g + weight_decay * p
             m += (g - m) * (1 - beta1)
             v.mul_(beta2).add_((1 - beta2) * g * g)
-            p -= s * m / (v.sqrt() * c + eps)
+            # written through the storage, as the kernel writes through the pointer: torch's
+            # version counter of the parameter does not move (Adam.step() has to move it)
+            p.numpy()[...] = (p - s * m / (v.sqrt() * c + eps)).numpy()
 
 
 class Recording(AdamSim):

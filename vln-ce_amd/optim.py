@@ -9,6 +9,11 @@ With `max_grad_norm` the step clips by the norm over ALL groups, as
 `torch.nn.utils.clip_grad_norm_(all parameters, max_grad_norm)` in front of `step()` would, and
 `optimizer.grad_norm` is the device scalar `clip_grad_norm_` returns; nothing is read back.  The
 one observable difference: `.grad` is read only and stays unclipped.
+
+The kernels write the parameters through raw pointers, which torch's version counters do not see,
+and every derived weight image and captured-graph key of this package is built on those counters;
+so `step()` ends by bumping `_version` of each parameter that took a step (the rule for any entry
+point that writes a parameter through its pointer: `torch.autograd.graph.increment_version`).
 """
 import math
 
@@ -186,4 +191,8 @@ class Adam(torch.optim.Adam):
                           group["weight_decay"], norm)
         if norm is not None:
             self.grad_norm = norm
+        # vlnce_adam_step wrote these parameters through their pointers: tell torch (one host call,
+        # no launch), or the weight images and graphs keyed on the old versions stay in use
+        torch.autograd.graph.increment_version(
+            [p for _, tab, gs, _, _ in work for p, g in zip(tab.ps, gs) if g is not None])
         return loss
