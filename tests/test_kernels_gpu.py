@@ -555,7 +555,10 @@ def test_rnn_seq_kernels_match_contract(hip, cfg):
         if r is None:
             continue
         for d in range(dirs):
-            close(g[d], r[d], 2e-4, what=f"{name}[{d}] {cfg}")
+            # 1e-5: what the header of rnn_seq.hip promises for its hardware exp2 / rcp gates (was
+            # 2e-4, above the ~1e-5 a missing plane product costs); test_rnn_seq_fp64_gpu.py holds
+            # the same kernels to fp64 at ~1e-6
+            close(g[d], r[d], 1e-5, what=f"{name}[{d}] {cfg}")
 
 
 @pytest.mark.parametrize("rnn_type,bidir,final_only", [("LSTM", True, False), ("LSTM", False, True),

@@ -1202,6 +1202,11 @@ class HipLib:
     def rnn_seq_supported(self, kind, H):
         return bool(self.dll.vlnce_rnn_seq_supported(kind, H))
 
+    # Packed-sequence RNN (csrc/rnn_seq.hip).  Contract of all five wrappers: 0 <= lengths[b] <= Lm.
+    # A length of 0 is a dead row (zeros, zero final state); a length above Lm is NOT checked and
+    # makes the reverse direction index past its buffers.  The first generation (rnn_seq_fwd /
+    # rnn_seq_bwd) wants out / dgi / dgh zero-filled by the caller; the second writes the zeros
+    # past each length itself (out_tm, seq, dgi, dgh), and rnn_seq_wgrad relies on them.
     def rnn_seq_fwd(self, kind, dirs, gi, w_hh, b_hh, lengths, out, h_final, gates_save, aux_save,
                     B, Lm, H):
         pa = self._parr
@@ -1230,6 +1235,7 @@ class HipLib:
                                                    ldy, act, _ptr(dx), _ptr(dw), _ptr(db), M, N, K,
                                                    _stream()), "vlnce_linear_rows_bwd")
 
+    # second generation: same contract, 0 <= lengths[b] <= Lm (see rnn_seq_fwd above)
     def rnn_seq_fwd2(self, kind, dirs, gi, w_hh, b_hh, lengths, out_tm, seq, seq_st, seq_sb, h_final,
                      gates_save, aux_save, B, Lm, H):
         pa = self._parr

@@ -15,6 +15,17 @@
 // t = len[b]-1 .. 0.  The backward kernel mirrors this with the transposed
 // recurrent weights and writes the pre-activation gate gradients for the big
 // dW / dX GEMMs that follow.
+//
+// CONTRACT on lengths, every entry point:  0 <= len[b] <= L.  A row of length 0 is never alive
+// (zeros everywhere, zero final state).  A length above L is NOT clamped where it matters:
+// zero_tails clamps, the step loops use the raw value, and the reverse walk tt = len-1-s would
+// index past the [L, B, *] buffers.  No caller produces one (L is the batch's longest length or
+// the padded width).
+// What the second-generation entry points guarantee past each length, whatever the buffers held
+// before the call: out_tm, seq (forward) and dgi, dgh (backward) are exact zeros; gates / aux are
+// not written there and never read there.  vlnce_rnn_seq_wgrad's shifted views (dW_hh) and its
+// sums over all L*B rows are correct only because of those zeros.
+// Held to the fp64 reference tests/rnn_seq_ref.py by tests/test_rnn_seq_fp64_gpu.py.
 #include "common.h"
 
 namespace {
