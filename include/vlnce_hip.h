@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 153 = this header */
+int vlnce_version(void); /* major*100 + minor; 154 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -72,6 +72,9 @@ const char* vlnce_last_error(void);
  *   "waypoint_dist"    0        read by the HOST (ABI 151): 1 = WaypointPolicy.evaluate_actions computes its
  *                               log-probability and entropies through vlnce_waypoint_eval / _bwd instead of
  *                               torch's distribution classes (the same as policy.fused_distributions = True)
+ *   "waypoint_act"     0        read by the HOST (ABI 154): 1 = WaypointPolicy.act draws and scores the whole action
+ *                               through vlnce_waypoint_act instead of torch's distribution classes (the same as
+ *                               policy.fused_act = True)
  * Set options between launches, not concurrently with them (relaxed atomics).  Unknown names
  * return non-zero. */
 int vlnce_set_option(const char* name, int value);
@@ -1139,6 +1142,84 @@ int vlnce_rollout_gather(const vlnce_rollout_gfield* fields, int n_fields, const
                          int T, vlnce_stream_t stream);
 int vlnce_ppo_advantages(const float* returns, const float* value_preds, float* adv, int T, int N,
                          int normalize, float eps, vlnce_stream_t stream);
+
+/* The rollout step of the Waypoint DD-PPO trainer on the device (ABI 154): everything
+ * WaypointPolicy.act does behind the net (waypoint_policy.py:129-247 over the distributions of
+ * models/utils.py) in ONE launch, and the trainer's pick of the observation history
+ * (ddppo_waypoint_trainer.py:190-200) in one more.
+ *
+ * vlnce_waypoint_act: one thread per row, every row in fp64, one rounding to fp32 per store, no atomics.
+ * It draws no random numbers itself: u [B,3] holds fp32 uniforms in [0, 1) (column 0 the panorama
+ * choice, 1 the offset, 2 the distance; NULL, and not read, when deterministic != 0), so the launch is a
+ * pure function of its inputs: two runs give the same bits.
+ *
+ * logits [B,P+1] are the RAW panorama logits; offset / distance are vlnce_wp_part descriptors as for
+ * vlnce_waypoint_eval, `element` unused, and for a discrete part lo / hi unused.  Per row:
+ *   panorama   c = the first maximum of logits[b,:] (deterministic), else with p_j = exp(z_j - max z) and
+ *              S = sum_j p_j added up in index order, the first k with sum_{j<=k} p_j > u0 * S, and the last
+ *              class of non-zero probability when there is none.  h = c mod P, gate = (c != P).
+ *   continuous loc = first[b,h], scale = sqrt(second[b,h]), [a, b] = ([lo, hi] - loc) / scale.  The element is
+ *              loc (deterministic), else loc + scale * ncdfinv(cdf(a) + u_k (cdf(b) - cdf(a))): the truncated
+ *              normal of the reference exactly, by inverse CDF (the device library's normcdfinv) where the
+ *              reference samples by rejection.  It is rounded to fp32 and clamped into [lo, hi].  mode = loc,
+ *              variance = scale^2 (1 + e2 - e1^2), e1 = (pdf(a) - pdf(b)) / mass, e2 = (a pdf(a) - b pdf(b)) / mass.
+ *   discrete   the element is the class drawn from first[b,h,:] by the panorama's rule with its own u_k
+ *              (deterministic: the first maximum), mode = the first maximum.  The variance is NaN, [B]: what
+ *              torch.distributions.Categorical.variance of the reference's class holds.
+ *   log_prob   log_softmax(z)[c] + gate * weight * logp_distance + gate * weight * logp_offset, each part's
+ *              term evaluated FROM THE ROUNDED fp32 ELEMENT by the formulas of vlnce_waypoint_eval (shared
+ *              code), so the number a rollout stores is the one evaluate_actions scores; a part of weight 0 adds
+ *              nothing, as the reference skips it.
+ *   metric     what the simulator gets: the continuous element itself, or the bin centre
+ *              bin_lo + k (bin_hi - bin_lo) / (K - 1) of class k.
+ * A part of weight 0 (`predict_* = False`, WaypointPolicy._draw) stores off_element (continuous) or class 0
+ * as its element, hands off_metric to the simulator, and has variance 0; its mode stays.
+ * norm_logits [B,P+1] = z - logsumexp(z): the returned distribution needs no further launch.
+ * theta = (h 2 pi / P + the offset's metric) mod 2 pi, in [0, 2 pi).
+ *
+ * flags[b] take the place of the reference's constructor assertions: VLNCE_WP_FLAG_PANO = a panorama logit
+ * that is not finite, and per part (shifted as for vlnce_waypoint_eval) VLNCE_WP_FLAG_LOC and
+ * VLNCE_WP_FLAG_VARIANCE at the chosen heading.  A flagged row is STOP in host_rows, NaN in every float
+ * output, pano = P and class 0.
+ * host_rows [B,8] fp32, the ONE buffer the host reads back: stop (0 | 1), r (the distance's metric), theta,
+ * the stored distance element in metres, the stored offset element in radians (what the trainer logs: they
+ * differ from r / theta's offset only for a part of weight 0), distance variance, offset variance, flags
+ * (small integers, exact in fp32).
+ *
+ * Shapes as vlnce_waypoint_eval_supported; anything else, and null pointers, are refused before launch.
+ *
+ * vlnce_waypoint_history_pick: one launch over a table of fields (at most VLNCE_WP_HISTORY_MAX_FIELDS),
+ * carried in the kernel arguments.  src_f is [B,P,E_f] with src_row_stride elements between environments
+ * (a slice of a larger arena), dst_f [B,E_f] contiguous, dtype VLNCE_TRAJ_F32 or VLNCE_TRAJ_U8:
+ *   dst_f[b,:] = src_f[b, pano[b], :] when 0 <= pano[b] < P, zeros otherwise (STOP, or a flagged row)
+ * pano (int64 [B]) is read on the device: the previous launch's output on the same stream.  Rows are dealt
+ * out in VLNCE_ROLLOUT_CHUNK pieces, one workgroup each; 16-byte accesses where both pointers, the row stride
+ * in bytes and E_f * elem_bytes are multiples of 16, one element per access otherwise.  Plain vector loads
+ * and stores only. */
+#define VLNCE_WP_HISTORY_MAX_FIELDS 8
+typedef struct {
+  double bin_lo;      /* discrete: the metric of class 0                                   */
+  double bin_hi;      /* discrete: the metric of class K - 1                               */
+  float off_metric;   /* weight 0: the metric handed to the simulator                      */
+  float off_element;  /* weight 0, continuous: the stored element                          */
+  void* element;      /* out: float [B] (continuous) or int64 [B] (discrete)               */
+  void* mode;         /* out: as element                                                   */
+  float* variance;    /* out: [B]                                                          */
+} vlnce_wp_act_part;
+typedef struct {
+  const void* src;      /* [B, P, E], environments src_row_stride elements apart           */
+  void* dst;            /* [B, E]                                                          */
+  long E;               /* elements per (environment, panorama), > 0                       */
+  long src_row_stride;  /* in elements, >= P * E                                           */
+  int dtype;            /* VLNCE_TRAJ_F32 | VLNCE_TRAJ_U8                                  */
+} vlnce_wp_history_field;
+int vlnce_waypoint_act_supported(int B, int P, int K_offset, int K_distance);
+int vlnce_waypoint_act(const float* logits, const vlnce_wp_part* offset, const vlnce_wp_part* distance,
+                       const vlnce_wp_act_part* offset_out, const vlnce_wp_act_part* distance_out,
+                       int deterministic, const float* u, int B, int P, int64_t* pano, float* log_prob,
+                       float* norm_logits, float* host_rows, int32_t* flags, vlnce_stream_t stream);
+int vlnce_waypoint_history_pick(const vlnce_wp_history_field* fields, int n_fields, const int64_t* pano,
+                                int B, int P, vlnce_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -156,6 +156,15 @@ class WpPartGrad(C.Structure):   # vlnce_wp_part_grad
     _fields_ = [("kind", _I), ("K", _I), ("weight", _F), ("d_first", _P), ("d_second", _P)]
 
 
+class WpActPart(C.Structure):   # vlnce_wp_act_part
+    _fields_ = [("bin_lo", _D), ("bin_hi", _D), ("off_metric", _F), ("off_element", _F), ("element", _P),
+                ("mode", _P), ("variance", _P)]
+
+
+class WpHistoryField(C.Structure):   # vlnce_wp_history_field
+    _fields_ = [("src", _P), ("dst", _P), ("E", _L), ("src_row_stride", _L), ("dtype", _I)]
+
+
 # ---- vlnce_grad_sumsq / vlnce_adam_step: the stable half of a tensor list
 ADAM_PARTIALS = 512   # VLNCE_ADAM_PARTIALS: doubles in the partials buffer
 
@@ -186,6 +195,12 @@ WP_FLAG_LOC, WP_FLAG_ELEMENT, WP_FLAG_VARIANCE, WP_FLAG_CLASS = 1, 2, 4, 8   # <
 WP_FLAG_SHIFT = {"offset": 4, "distance": 8}
 WaypointPart = collections.namedtuple("WaypointPart", "kind K lo hi weight first second element")
 WaypointPartGrad = collections.namedtuple("WaypointPartGrad", "kind K weight d_first d_second")
+# ---- vlnce_waypoint_act: what a component needs beyond its WaypointPart (the metric of its classes, the
+# `predict_* = False` constants) and its three outputs
+WaypointActPart = collections.namedtuple("WaypointActPart",
+                                         "bin_lo bin_hi off_metric off_element element mode variance")
+WP_ACT_ROW = 8   # floats of a host row: stop, r, theta, distance, offset, distance var, offset var, flags
+WP_HISTORY_MAX_FIELDS = 8   # VLNCE_WP_HISTORY_MAX_FIELDS
 
 
 def waypoint_saved_planes(P, parts):
@@ -258,6 +273,10 @@ _SIGNATURES = {
                                  _P]),
     "vlnce_waypoint_eval_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(WpPartGrad),
                                      C.POINTER(WpPartGrad), _I, _I, _P, _P]),
+    "vlnce_waypoint_act_supported": (_I, [_I, _I, _I, _I]),
+    "vlnce_waypoint_act": (_I, [_P, C.POINTER(WpPart), C.POINTER(WpPart), C.POINTER(WpActPart),
+                                C.POINTER(WpActPart), _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "vlnce_waypoint_history_pick": (_I, [C.POINTER(WpHistoryField), _I, _P, _I, _I, _P]),
     "vlnce_adam_supported": (_I, [_I, _L]),
     "vlnce_adam_max_tensors": (_I, []),
     "vlnce_adam_chunk": (_I, []),
@@ -423,7 +442,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 153  # include/vlnce_hip.h
+    ABI = 154  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -443,7 +462,7 @@ class HipLib:
     # the VLNCE_* variables of INTEGRATION.md section 8 are translated here, once, at load
     OPTION_NAMES = ("conv_math", "p3", "p3_tile", "s3", "u3", "u3_waves", "x3_tile", "igemm_tile",
                     "igemm_nobuf", "igemm_no_splitk", "wgrad_tile", "rollout_one_xcd", "m3", "r3",
-                    "s3_wgs", "waypoint_dist")
+                    "s3_wgs", "waypoint_dist", "waypoint_act")
 
     def _options_from_env(self):
         for name in self.OPTION_NAMES:
@@ -910,6 +929,62 @@ class HipLib:
         self._check(self.dll.vlnce_waypoint_eval_bwd(
             *[_ptr(g) for g in grads], _ptr(pano), _ptr(saved), _ptr(flags), C.byref(descs[0]),
             C.byref(descs[1]), B, P, _ptr(d_logits), _stream()), "vlnce_waypoint_eval_bwd")
+
+    def waypoint_act_supported(self, B, P, K_offset, K_distance):
+        return bool(self.dll.vlnce_waypoint_act_supported(int(B), int(P), int(K_offset),
+                                                          int(K_distance)))
+
+    def waypoint_act(self, logits, offset, distance, offset_out, distance_out, deterministic, u, B, P,
+                     pano, log_prob, norm_logits, host_rows, flags):
+        """WaypointPolicy.act behind the net in one launch: offset / distance are WaypointPart tuples
+        (element unused), offset_out / distance_out WaypointActPart tuples whose element / mode (fp32 or
+        int64 [B]) and variance (fp32 [B]) are written; u [B, 3] fp32 uniforms (None when
+        deterministic); pano int64 [B], log_prob [B], norm_logits [B, P+1], host_rows [B, WP_ACT_ROW],
+        flags int32 [B]"""
+        f32 = [logits, log_prob, norm_logits, host_rows] + ([] if u is None else [u])
+        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in f32)
+        assert logits.numel() == B * (P + 1) and norm_logits.numel() == B * (P + 1)
+        assert log_prob.numel() == B and host_rows.numel() == B * WP_ACT_ROW
+        assert u is None or u.numel() == B * 3
+        assert pano.dtype == torch.int64 and pano.numel() == B and pano.is_contiguous()
+        assert flags.dtype == torch.int32 and flags.numel() == B and flags.is_contiguous()
+        descs, outs = [], []
+        for p, o in ((offset, offset_out), (distance, distance_out)):
+            n = B * P * (p.K if p.kind == WP_DISCRETE else 1)
+            elem = torch.float32 if p.kind == WP_CONTINUOUS else torch.int64
+            assert p.first is None or (p.first.dtype == torch.float32 and p.first.numel() == n
+                                       and p.first.is_contiguous())
+            assert p.second is None or (p.second.dtype == torch.float32 and p.second.numel() == B * P
+                                        and p.second.is_contiguous())
+            for t in (o.element, o.mode):
+                assert t is None or (t.dtype == elem and t.numel() == B and t.is_contiguous())
+            assert o.variance is None or (o.variance.dtype == torch.float32 and o.variance.numel() == B
+                                          and o.variance.is_contiguous())
+            descs.append(WpPart(int(p.kind), int(p.K), float(p.lo), float(p.hi), float(p.weight),
+                                _ptr(p.first), _ptr(p.second), None))
+            outs.append(WpActPart(float(o.bin_lo), float(o.bin_hi), float(o.off_metric),
+                                  float(o.off_element), _ptr(o.element), _ptr(o.mode), _ptr(o.variance)))
+        self._check(self.dll.vlnce_waypoint_act(
+            _ptr(logits), C.byref(descs[0]), C.byref(descs[1]), C.byref(outs[0]), C.byref(outs[1]),
+            int(bool(deterministic)), _ptr(u), B, P, _ptr(pano), _ptr(log_prob), _ptr(norm_logits),
+            _ptr(host_rows), _ptr(flags), _stream()), "vlnce_waypoint_act")
+
+    def waypoint_history_pick(self, fields, pano, B, P):
+        """one launch: for every (src, dst) pair -- src [B, P, ...] whose environments may be strided (a
+        slice of an arena), dst [B, ...] contiguous, both fp32 or both uint8 --
+        dst[b] = src[b, pano[b]] when 0 <= pano[b] < P, zeros otherwise; pano int64 [B] on the device"""
+        assert pano.dtype == torch.int64 and pano.numel() == B and pano.is_contiguous()
+        arr = (WpHistoryField * len(fields))()
+        for a, (src, dst) in zip(arr, fields):
+            assert src.dtype == dst.dtype and src.dtype in (torch.float32, torch.uint8)
+            assert src.shape[0] == B and src.shape[1] == P and src[0].is_contiguous()
+            assert dst.is_contiguous() and dst.shape == (B,) + tuple(src.shape[2:])
+            a.src, a.dst = _ptr(src), _ptr(dst)
+            a.E = src[0, 0].numel()
+            a.src_row_stride = src.stride(0) if B > 1 else P * a.E
+            a.dtype = self._TRAJ[src.dtype]
+        self._check(self.dll.vlnce_waypoint_history_pick(arr, len(fields), _ptr(pano), int(B), int(P),
+                                                         _stream()), "vlnce_waypoint_history_pick")
 
     def adam_supported(self, n_tensors, n_chunks):
         return bool(self.dll.vlnce_adam_supported(int(n_tensors), int(n_chunks)))

@@ -52,7 +52,9 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // over a list of tensors in two launches; csrc/optim.hip).
 // 153: vlnce_rollout_copy / _copy_supported / _gather, vlnce_ppo_advantages (the DD-PPO rollout storage's insert,
 // after_update, minibatch gather and advantages, one launch each; csrc/rollout.hip).
-extern "C" int vlnce_version(void) { return 153; }
+// 154: vlnce_waypoint_act / _act_supported, vlnce_waypoint_history_pick (WaypointPolicy.act behind the net in one launch,
+// the trainer's observation-history pick in one more; csrc/waypoint_act.hip); option "waypoint_act".
+extern "C" int vlnce_version(void) { return 154; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)
@@ -66,9 +68,10 @@ const OptDef kOpts[VLNCE_OPT_COUNT] = {
     {"u3", 1},          {"u3_waves", 8},    {"x3_tile", 0},         {"igemm_tile", 0},
     {"igemm_nobuf", 0}, {"igemm_no_splitk", 0}, {"wgrad_tile", 64}, {"rollout_one_xcd", 0},
     {"m3", 1},          {"r3", 1},          {"s3_wgs", 0},          {"waypoint_dist", 0},
+    {"waypoint_act", 0},
 };
 std::atomic<int> g_opt[VLNCE_OPT_COUNT] = {
-    {2}, {2}, {0}, {1}, {1}, {8}, {0}, {0}, {0}, {0}, {64}, {0}, {1}, {1}, {0}, {0},
+    {2}, {2}, {0}, {1}, {1}, {8}, {0}, {0}, {0}, {0}, {64}, {0}, {1}, {1}, {0}, {0}, {0},
 };
 int opt_index(const char* name) {
   if (name)

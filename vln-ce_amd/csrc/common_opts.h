@@ -24,6 +24,7 @@ enum {
   VLNCE_OPT_R3,               // regenerating block end (conv_r3_kernel): 0 off, 1 the layers measured faster (default), 2 every shape it covers
   VLNCE_OPT_S3_WGS,           // conv_s3_kernel / conv_r3_kernel: 0 = one workgroup per CU, n = at most n workgroups
   VLNCE_OPT_WAYPOINT_DIST,    // read by the host: 1 = WaypointPolicy.evaluate_actions through vlnce_waypoint_eval (default 0)
+  VLNCE_OPT_WAYPOINT_ACT,     // read by the host: 1 = WaypointPolicy.act through vlnce_waypoint_act (default 0)
   VLNCE_OPT_COUNT
 };
 int vlnce_opt(int id);

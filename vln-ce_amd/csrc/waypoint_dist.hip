@@ -18,18 +18,9 @@
 
 #include <limits>
 
-#include "common.h"
+#include "waypoint_math.h"
 
 namespace {
-
-constexpr int WP_THREADS = 64;
-constexpr int WP_MAX_P = 63;
-constexpr int WP_MAX_K = 32;
-
-constexpr double WP_SQRT_2PI = 2.50662827463100050242;
-constexpr double WP_INV_SQRT_2PI = 0.398942280401432677940;
-constexpr double WP_INV_SQRT2 = 0.707106781186547524401;
-constexpr double WP_HALF_LOG_2PIE = 1.41893853320467274178;   // log(2 pi e) / 2
 
 __host__ __device__ inline int wp_saved_planes(int kind, int K) {
   return kind == VLNCE_WP_CONTINUOUS ? 4 : kind == VLNCE_WP_DISCRETE ? 2 * K : 0;
@@ -65,13 +56,10 @@ __device__ inline void wp_categorical(const float* __restrict__ z, int n, long c
 // derivatives with respect to loc and to the VARIANCE (scale = sqrt(variance))
 __device__ inline void wp_truncated_normal(double loc, double var, double v, double lo, double hi,
                                            double* logp, double* ent, double d[4]) {
-  const double s = sqrt(var);
-  const double a = (lo - loc) / s, b = (hi - loc) / s;
-  const double mass = 0.5 * (erf(b * WP_INV_SQRT2) - erf(a * WP_INV_SQRT2));
-  const double pa = exp(-0.5 * a * a) * WP_INV_SQRT_2PI, pb = exp(-0.5 * b * b) * WP_INV_SQRT_2PI;
-  const double e1 = (pa - pb) / mass, e2 = (a * pa - b * pb) / mass;
-  const double z = (v - loc) / s;
-  *logp = -0.5 * z * z - log(WP_SQRT_2PI * s * mass);
+  const WpTruncated t = wp_truncated_terms(loc, var, lo, hi);
+  const double s = t.s, a = t.a, b = t.b, mass = t.mass, pa = t.pa, pb = t.pb, e1 = t.e1, e2 = t.e2;
+  double z;
+  *logp = wp_truncated_logp(t, loc, v, &z);
   *ent = WP_HALF_LOG_2PIE + log(s * mass) + 0.5 * e2;
   // d a / d loc = d b / d loc = -1 / s; d a / d s = -a / s, d b / d s = -b / s;
   // d mass / d loc = (pa - pb) / s; d mass / d s = (a pa - b pb) / s; d (x pdf(x)) / d x = pdf(x) (1 - x^2)
@@ -242,11 +230,6 @@ __global__ __launch_bounds__(WP_THREADS) void waypoint_eval_bwd_kernel(
   wp_part_bwd(offset, b, h, flagged, gl, g_ent_offset, P, B, pano, sv);
   sv += (long)wp_saved_planes(offset.kind, offset.K) * B;
   wp_part_bwd(distance, b, h, flagged, gl, g_ent_distance, P, B, pano, sv);
-}
-
-bool wp_kind_ok(int kind, int K) {
-  if (kind == VLNCE_WP_DISCRETE) return K >= 1 && K <= WP_MAX_K;
-  return kind == VLNCE_WP_ABSENT || kind == VLNCE_WP_CONTINUOUS;
 }
 
 }  // namespace

@@ -82,6 +82,52 @@ class PPOLossFn(torch.autograd.Function):
         return (*out, None, None, None, None, None, None)
 
 
+def act_for_rollout(policy, rollouts, deterministic=False):
+    """The action half of `_collect_rollout_step` (ddppo_waypoint_trainer.py:160-220) over any storage
+    with the arenas (vlnce_amd.ActionDictRolloutStorage, or the reference's own class): slices the
+    arenas at rollouts.step, calls policy.act, picks each environment's chosen panorama frame as the
+    next step's rgb / depth history (zeros for STOP) and collects the logging predictions of the
+    environments that go on.  Returns (act()'s 8-tuple, {"rgb", "depth"} history, logging_predictions).
+
+    When act() took its one-launch path (policy.fused_act / the "waypoint_act" option) the history is
+    ONE launch that reads the choice on the device, and the predictions come from the host rows act()
+    already read back: no second synchronisation.  Otherwise this is the reference's loop."""
+    from . import waypoint_act
+
+    step = rollouts.step
+    observation = {k: v[step] for k, v in rollouts.observations.items()}
+    prev_actions = {k: v[step] for k, v in rollouts.prev_actions.items()}
+    with torch.no_grad():
+        outputs = policy.act(observation, rollouts.recurrent_hidden_states[step], prev_actions,
+                             rollouts.masks[step], deterministic=deterministic)
+    _, actions, elements, _, variances, _, _, _ = outputs
+    frames = {k: observation[k] for k in ("rgb", "depth")}
+    predictions = {k: [] for k in ("distance_pred", "offset_pred", "distance_var", "offset_var")}
+    rows = getattr(policy, "last_act_rows", None)
+    if rows is not None:
+        history = waypoint_act.history_pick(frames, elements["pano"])
+        for row in rows:
+            if not row[waypoint_act.ROW_STOP]:
+                predictions["distance_pred"].append(row[waypoint_act.ROW_DISTANCE])
+                predictions["offset_pred"].append(row[waypoint_act.ROW_OFFSET])
+                predictions["distance_var"].append(row[waypoint_act.ROW_DISTANCE_VAR])
+                predictions["offset_var"].append(row[waypoint_act.ROW_OFFSET_VAR])
+        return outputs, history, predictions
+    history = {k: torch.zeros_like(v[:, 0]) for k, v in frames.items()}
+    for i, action in enumerate(actions):
+        if action["action"] == "STOP":
+            continue
+        idx = elements["pano"][i]
+        for k, v in frames.items():
+            history[k][i] = v[i, idx]
+        for part, to_metric in (("distance", policy.net.distance_to_continuous),
+                                ("offset", policy.net.offset_to_continuous)):
+            predictions[part + "_pred"].append(to_metric(elements[part][i]).item())
+            var = variances[part]
+            predictions[part + "_var"].append(var[i].item() if type(var) is torch.Tensor else var)
+    return outputs, history, predictions
+
+
 def _clips_itself(optimizer):
     """vlnce_amd.optim.Adam(max_grad_norm=...) clips inside its own step (one norm launch)"""
     from .optim import Adam

@@ -9,7 +9,8 @@ pair of parallel methods each; the distribution math is O(N x 13) scalars and st
 (SURVEY.md 2.1), the net runs on the HIP kernels.  Opt-in (`fused_distributions`): evaluate_actions
 computes its log-probability and entropies in one HIP launch, and one more backward, with no host
 synchronisation (waypoint_dist.py); the reference's assertions are then read on demand
-(`check_eval_flags`).
+(`check_eval_flags`).  Opt-in (`fused_act`): act() draws and scores the whole action in one HIP
+launch and reads ONE [B, 8] buffer back for the simulator's actions (waypoint_act.py).
 """
 import math
 from typing import NamedTuple
@@ -17,7 +18,7 @@ from typing import NamedTuple
 import torch
 
 from .policy import Policy
-from . import ops, waypoint_dist
+from . import ops, waypoint_act, waypoint_dist
 from .registry import baseline_registry
 from .utils import CustomFixedCategorical, TruncatedNormal, batched_index_select
 from .waypoint_predictors import WaypointPredictionNet
@@ -46,6 +47,9 @@ class WaypointPolicy(Policy):
     # True: evaluate_actions takes the one-launch path (also switched on by the dispatch option
     # "waypoint_dist" / VLNCE_WAYPOINT_DIST=1); a shape the kernel does not cover keeps the torch path
     fused_distributions = False
+    # True: act() takes the one-launch path (also switched on by the dispatch option "waypoint_act" /
+    # VLNCE_WAYPOINT_ACT=1); a shape the kernel does not cover keeps the torch path
+    fused_act = False
 
     def __init__(self, observation_space, action_space, model_config):
         net = WaypointPredictionNet(observation_space=observation_space, model_config=model_config)
@@ -54,6 +58,7 @@ class WaypointPolicy(Policy):
         self.wypt_cfg = model_config.WAYPOINT
         self._offset_limit = math.pi / model_config.num_panos
         self.eval_flags = None   # int32 [B] of the last fused evaluate_actions (check_eval_flags)
+        self.last_act_rows = None   # host rows [B][8] of the last act(), when it took the fused path
 
     @classmethod
     def from_config(cls, config, observation_space, action_space):
@@ -105,8 +110,51 @@ class WaypointPolicy(Policy):
                 for s, r, th in rows]
 
     # ------------------------------------------------------------------ plugin surface
+    def _fused_act(self, batch):
+        """the spec when this act() takes the one-launch path, else None"""
+        lib = ops.L()
+        if not (self.fused_act or (hasattr(lib, "effective_option")
+                                   and lib.effective_option("waypoint_act"))):
+            return None
+        P, kinds = spec = self._eval_spec()
+        if not lib.waypoint_act_supported(batch, P, kinds["offset"][1], kinds["distance"][1]):
+            return None
+        return spec
+
+    def _act_extras(self):
+        """{part: (metric of class 0, metric of the last class, the `predict_* = False` constants)}"""
+        return {part: (*self._bounds(part), off_metric, off_element)
+                for part, (_, _, off_metric, off_element) in self._PARTS.items()}
+
+    def _act_fused(self, spec, observations, rnn_states, prev_actions, masks, deterministic):
+        (logits, off_a, off_b, dist_a, dist_b, features, rnn_states_out) = self.net(
+            observations, rnn_states, prev_actions, masks, raw_pano_logits=True)
+        res = waypoint_act.launch(logits, off_a, off_b, dist_a, dist_b, spec, self._act_extras(),
+                                  deterministic)
+        value = self.critic(features)
+        rows = self.last_act_rows = res.host_rows.tolist()   # the one read-back of this call
+        bits = 0
+        for row in rows:
+            bits |= int(row[waypoint_act.ROW_FLAGS])
+        msg = waypoint_act.flag_errors(bits, {p: self._bounds(p) for p in self._PARTS})
+        if msg is not None:
+            raise AssertionError(msg)
+        actions = [{"action": "STOP"} if row[waypoint_act.ROW_STOP] else
+                   {"action": {"action": "GO_TOWARD_POINT",
+                               "action_args": {"r": row[waypoint_act.ROW_R],
+                                               "theta": row[waypoint_act.ROW_THETA]}}}
+                   for row in rows]
+        elements = {"pano": res.pano, "offset": res.elements["offset"],
+                    "distance": res.elements["distance"]}
+        return (value, actions, elements, res.modes, res.variances, res.log_prob, rnn_states_out,
+                CustomFixedCategorical.from_normalized(res.norm_logits))
+
     def act(self, observations, rnn_states, prev_actions, masks, deterministic=False):
         n_pano = self._config.num_panos
+        self.last_act_rows = None
+        spec = self._fused_act(masks.shape[0])
+        if spec is not None:
+            return self._act_fused(spec, observations, rnn_states, prev_actions, masks, deterministic)
         (heading_dist, off_a, off_b, dist_a, dist_b, features, rnn_states_out) = self.net(
             observations, rnn_states, prev_actions, masks)
         choice = heading_dist.mode() if deterministic else heading_dist.sample()
