@@ -30,7 +30,7 @@ typedef void* vlnce_stream_t;
 
 enum { VLNCE_ACT_NONE = 0, VLNCE_ACT_RELU = 1, VLNCE_ACT_SIGMOID = 2, VLNCE_ACT_TANH = 3 };
 
-int vlnce_version(void); /* major*100 + minor; 154 = this header */
+int vlnce_version(void); /* major*100 + minor; 155 = this header */
 int vlnce_option_count(void);              /* length of vlnce_prologue.options                        */
 int vlnce_option_index(const char* name);  /* index of a named dispatch option in it, -1 if unknown   */
 const char* vlnce_last_error(void);
@@ -1220,6 +1220,56 @@ int vlnce_waypoint_act(const float* logits, const vlnce_wp_part* offset, const v
                        float* norm_logits, float* host_rows, int32_t* flags, vlnce_stream_t stream);
 int vlnce_waypoint_history_pick(const vlnce_wp_history_field* fields, int n_fields, const int64_t* pano,
                                 int B, int P, vlnce_stream_t stream);
+
+/* The trunk-feature cache of the Waypoint DD-PPO loop (ABI 155).  Both visual encoders of the Waypoint
+ * trainer are frozen (models/encoders/resnet_encoders.py:46,142) and in eval mode while rollouts are
+ * collected and while the agent is updated (ddppo_waypoint_trainer.py:496,526-530): a trunk's output is a
+ * fixed function of one frame.  A rollout therefore keeps the trunk outputs beside the frames, and these
+ * two entry points move them; both are pure data movement over a table of fp32 fields (at most
+ * VLNCE_WP_FEATURE_MAX_FIELDS, carried in the kernel arguments) by the recipe of vlnce_rollout_copy and
+ * vlnce_waypoint_history_pick: rows dealt out in VLNCE_ROLLOUT_CHUNK pieces, one workgroup each; 16-byte
+ * accesses where every pointer of the field, every stride in bytes and F_f * 4 are multiples of 16, one
+ * element per access otherwise; plain vector loads and stores only; no host synchronisation, no
+ * allocation, nothing staged that a later call could overwrite.  Strides are in elements.  Refused before
+ * anything is launched (non-zero, vlnce_last_error): a null pointer, n_fields outside
+ * 1..VLNCE_WP_FEATURE_MAX_FIELDS, B <= 0, P <= 0, F_f <= 0, a stride smaller than its row, a pointer off
+ * its 4 bytes, a mask dtype other than the two named.
+ *
+ * vlnce_waypoint_feature_pick: the next step's history features.  src_f is [B,P,F_f] with src_row_stride
+ * elements between environments (a slice of an arena), zero_f [F_f], dst_f [B,F_f] contiguous:
+ *   dst_f[b,:] = src_f[b, pano[b], :] when 0 <= pano[b] < P, zero_f otherwise (STOP, or a flagged row)
+ * pano (int64 [B]) is read on the device: vlnce_waypoint_act's output on the same stream.  zero_f is the
+ * trunk's output for an all-zero frame: what the encoder makes of the zeros vlnce_waypoint_history_pick
+ * stores for such a row.
+ *
+ * vlnce_waypoint_feature_rows: the encoder's batch of B * (P + 1) frames, from features
+ * (waypoint_predictors.py:330-341: the history frame times its not-done mask behind the panorama).
+ * pano_f [B,P,F_f] and hist_f [B,F_f], each with its own row stride, zero_f [F_f], out_f [B,P+1,F_f]
+ * contiguous:
+ *   out_f[b,j,:] = pano_f[b,j,:] for j < P;   out_f[b,P,:] = hist_f[b,:] when masks[b] != 0, else zero_f
+ * masks [B] is uint8 (mask_dtype VLNCE_TRAJ_U8) or fp32 (VLNCE_TRAJ_F32), the two dtypes in which the
+ * storage and the net hold it. */
+#define VLNCE_WP_FEATURE_MAX_FIELDS 8
+typedef struct {
+  const float* src;     /* [B, P, F], environments src_row_stride elements apart           */
+  const float* zero;    /* [F]                                                             */
+  float* dst;           /* [B, F]                                                          */
+  long F;               /* elements per (environment, panorama), > 0                       */
+  long src_row_stride;  /* in elements, >= P * F                                           */
+} vlnce_wp_feature_pick_field;
+typedef struct {
+  const float* pano;    /* [B, P, F], environments pano_row_stride elements apart          */
+  const float* hist;    /* [B, F], environments hist_row_stride elements apart             */
+  const float* zero;    /* [F]                                                             */
+  float* out;           /* [B, P + 1, F]                                                   */
+  long F;               /* elements per (environment, panorama), > 0                       */
+  long pano_row_stride; /* in elements, >= P * F                                           */
+  long hist_row_stride; /* in elements, >= F                                               */
+} vlnce_wp_feature_rows_field;
+int vlnce_waypoint_feature_pick(const vlnce_wp_feature_pick_field* fields, int n_fields, const int64_t* pano,
+                                int B, int P, vlnce_stream_t stream);
+int vlnce_waypoint_feature_rows(const vlnce_wp_feature_rows_field* fields, int n_fields, const void* masks,
+                                int mask_dtype, int B, int P, vlnce_stream_t stream);
 
 #ifdef __cplusplus
 }

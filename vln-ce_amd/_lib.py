@@ -9,6 +9,7 @@ lives under tests/ and is never importable from the product.)
 """
 import collections
 import ctypes as C
+import math
 import os
 import threading
 
@@ -165,6 +166,15 @@ class WpHistoryField(C.Structure):   # vlnce_wp_history_field
     _fields_ = [("src", _P), ("dst", _P), ("E", _L), ("src_row_stride", _L), ("dtype", _I)]
 
 
+class WpFeaturePickField(C.Structure):   # vlnce_wp_feature_pick_field
+    _fields_ = [("src", _P), ("zero", _P), ("dst", _P), ("F", _L), ("src_row_stride", _L)]
+
+
+class WpFeatureRowsField(C.Structure):   # vlnce_wp_feature_rows_field
+    _fields_ = [("pano", _P), ("hist", _P), ("zero", _P), ("out", _P), ("F", _L), ("pano_row_stride", _L),
+                ("hist_row_stride", _L)]
+
+
 # ---- vlnce_grad_sumsq / vlnce_adam_step: the stable half of a tensor list
 ADAM_PARTIALS = 512   # VLNCE_ADAM_PARTIALS: doubles in the partials buffer
 
@@ -201,6 +211,7 @@ WaypointActPart = collections.namedtuple("WaypointActPart",
                                          "bin_lo bin_hi off_metric off_element element mode variance")
 WP_ACT_ROW = 8   # floats of a host row: stop, r, theta, distance, offset, distance var, offset var, flags
 WP_HISTORY_MAX_FIELDS = 8   # VLNCE_WP_HISTORY_MAX_FIELDS
+WP_FEATURE_MAX_FIELDS = 8   # VLNCE_WP_FEATURE_MAX_FIELDS
 
 
 def waypoint_saved_planes(P, parts):
@@ -277,6 +288,8 @@ _SIGNATURES = {
     "vlnce_waypoint_act": (_I, [_P, C.POINTER(WpPart), C.POINTER(WpPart), C.POINTER(WpActPart),
                                 C.POINTER(WpActPart), _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vlnce_waypoint_history_pick": (_I, [C.POINTER(WpHistoryField), _I, _P, _I, _I, _P]),
+    "vlnce_waypoint_feature_pick": (_I, [C.POINTER(WpFeaturePickField), _I, _P, _I, _I, _P]),
+    "vlnce_waypoint_feature_rows": (_I, [C.POINTER(WpFeatureRowsField), _I, _P, _I, _I, _I, _P]),
     "vlnce_adam_supported": (_I, [_I, _L]),
     "vlnce_adam_max_tensors": (_I, []),
     "vlnce_adam_chunk": (_I, []),
@@ -442,7 +455,7 @@ class HipLib:
 
     name = "hip"
 
-    ABI = 154  # include/vlnce_hip.h
+    ABI = 155  # include/vlnce_hip.h
 
     def __init__(self, path=LIB_PATH):
         self.dll = load_cdll(path)
@@ -985,6 +998,46 @@ class HipLib:
             a.dtype = self._TRAJ[src.dtype]
         self._check(self.dll.vlnce_waypoint_history_pick(arr, len(fields), _ptr(pano), int(B), int(P),
                                                          _stream()), "vlnce_waypoint_history_pick")
+
+    @staticmethod
+    def _feature_rows(t, lead, F):
+        """t [B, *lead, ...] fp32 whose rows are contiguous inside: its row stride in elements"""
+        assert t.dtype == torch.float32 and tuple(t.shape[1:1 + len(lead)]) == tuple(lead)
+        assert t[0].is_contiguous() and t[0].numel() == math.prod(lead) * F
+        return int(t.stride(0)) if t.size(0) > 1 else t[0].numel()
+
+    def waypoint_feature_pick(self, fields, pano, B, P):
+        """one launch: for every (src, zero, dst) -- src [B, P, ...] fp32 whose environments may be
+        strided (a slice of an arena), zero [...] and dst [B, ...] contiguous --
+        dst[b] = src[b, pano[b]] when 0 <= pano[b] < P, zero otherwise; pano int64 [B] on the device"""
+        assert pano.dtype == torch.int64 and pano.numel() == B and pano.is_contiguous()
+        arr = (WpFeaturePickField * len(fields))()
+        for a, (src, zero, dst) in zip(arr, fields):
+            F = zero.numel()
+            assert zero.dtype == dst.dtype == torch.float32 and zero.is_contiguous()
+            assert dst.is_contiguous() and dst.shape[0] == B and dst.numel() == B * F
+            a.src_row_stride = self._feature_rows(src, (P,), F)
+            a.src, a.zero, a.dst, a.F = _ptr(src), _ptr(zero), _ptr(dst), F
+        self._check(self.dll.vlnce_waypoint_feature_pick(arr, len(fields), _ptr(pano), int(B), int(P),
+                                                         _stream()), "vlnce_waypoint_feature_pick")
+
+    def waypoint_feature_rows(self, fields, masks, B, P):
+        """one launch: for every (pano, hist, zero, out) -- pano [B, P, ...] and hist [B, ...] fp32, each
+        possibly strided between environments, zero [...] and out [B, P + 1, ...] contiguous --
+        out[b, :P] = pano[b]; out[b, P] = hist[b] when masks[b] != 0, zero otherwise; masks uint8 or
+        fp32 [B] on the device"""
+        assert masks.dtype in (torch.uint8, torch.float32) and masks.numel() == B and masks.is_contiguous()
+        arr = (WpFeatureRowsField * len(fields))()
+        for a, (pano, hist, zero, out) in zip(arr, fields):
+            F = zero.numel()
+            assert zero.dtype == out.dtype == torch.float32 and zero.is_contiguous()
+            assert out.is_contiguous() and out.shape[0] == B and out.numel() == B * (P + 1) * F
+            a.pano_row_stride = self._feature_rows(pano, (P,), F)
+            a.hist_row_stride = self._feature_rows(hist, (), F)
+            a.pano, a.hist, a.zero, a.out, a.F = _ptr(pano), _ptr(hist), _ptr(zero), _ptr(out), F
+        self._check(self.dll.vlnce_waypoint_feature_rows(arr, len(fields), _ptr(masks),
+                                                         self._TRAJ[masks.dtype], int(B), int(P), _stream()),
+                    "vlnce_waypoint_feature_rows")
 
     def adam_supported(self, n_tensors, n_chunks):
         return bool(self.dll.vlnce_adam_supported(int(n_tensors), int(n_chunks)))

@@ -54,7 +54,10 @@ extern "C" const char* vlnce_last_error(void) { return g_err; }
 // after_update, minibatch gather and advantages, one launch each; csrc/rollout.hip).
 // 154: vlnce_waypoint_act / _act_supported, vlnce_waypoint_history_pick (WaypointPolicy.act behind the net in one launch,
 // the trainer's observation-history pick in one more; csrc/waypoint_act.hip); option "waypoint_act".
-extern "C" int vlnce_version(void) { return 154; }
+// 155: vlnce_waypoint_feature_pick / _feature_rows (the trunk-feature cache of the Waypoint DD-PPO loop: the
+// history features of the next step and the [B, P + 1, F] encoder batch, one launch each;
+// csrc/waypoint_features.hip).
+extern "C" int vlnce_version(void) { return 155; }
 
 // ---- dispatch options: one int per name, process-wide, relaxed atomics (a tuning / test knob,
 // not a synchronisation point: set them before the launches they are meant for)

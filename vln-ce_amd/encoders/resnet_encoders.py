@@ -666,6 +666,10 @@ class TorchVisionResNet(nn.Module):
     def trunk_parameters(self):
         return self.cnn._plist()
 
+    def trunk_norms(self):
+        """the trunk's BatchNorm layers (their mode is part of what a cached feature depends on)"""
+        return self.cnn._norms
+
     def trunk_ready(self, observations):
         self.cnn.input_scale = self._input_transform(_GraphRunner._parts(observations["rgb"])[0].device)
         return self.cnn.graph_ready(observations["rgb"])
@@ -900,6 +904,14 @@ class VlnResnetDepthEncoder(nn.Module):
 
     def trunk_parameters(self):
         return self.visual_encoder._plist()
+
+    def trunk_norms(self):
+        """the trunk's GroupNorm layers (per sample in either mode)"""
+        norms = self.__dict__.get("_trunk_norm_list")
+        if norms is None:
+            norms = [m for m in self.visual_encoder.modules() if isinstance(m, nn.GroupNorm)]
+            object.__setattr__(self, "_trunk_norm_list", norms)
+        return norms
 
     def trunk_ready(self, observations):
         return self.visual_encoder.graph_ready(observations["depth"])

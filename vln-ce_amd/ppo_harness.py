@@ -82,6 +82,56 @@ class PPOLossFn(torch.autograd.Function):
         return (*out, None, None, None, None, None, None)
 
 
+SENSORS = ("rgb", "depth")
+
+
+def _step_observation(policy, rollouts):
+    """rollouts.observations at rollouts.step as the net takes them, and what to do after the forward.
+    For a storage with trunk-feature arenas (ActionDictRolloutStorage(trunk_features=...)): the stored
+    history features always stand in for the history frames; the stored panorama features stand in
+    for the panorama frames when the row holds them under the net's current trunk_cache_key() (row 0
+    after after_update); otherwise the forward runs the trunks on the panorama and `store()` writes
+    their outputs into the row."""
+    step = rollouts.step
+    observation = {k: v[step] for k, v in rollouts.observations.items()}
+    if not getattr(rollouts, "has_trunk_features", False):
+        return observation, lambda: None
+    net = policy.net
+    key = net.trunk_cache_key()
+    if rollouts.trunk_key != key:
+        # nothing made under another key is used: the row's history features are made again
+        if rollouts.trunk_key is not None:
+            for s in SENSORS:
+                observation[s + "_history_features"].copy_(net._trunk_rows(s, observation[s + "_history"]))
+        rollouts.trunk_valid = [False] * len(rollouts.trunk_valid)
+        rollouts.trunk_key = key
+    observation["trunk_feature_key"] = key
+    if rollouts.trunk_valid[step]:
+        return observation, lambda: None
+    arenas = {s: observation.pop(s + "_features") for s in SENSORS}
+
+    def store():
+        for s in SENSORS:
+            arenas[s].copy_(net.last_trunk_features[s])
+        rollouts.trunk_valid[step] = True
+
+    return observation, store
+
+
+def bootstrap_value(policy, rollouts):
+    """The value of the row behind the last collected step (ddppo_waypoint_trainer.py:287-299), for
+    compute_returns.  With trunk-feature arenas the row's panorama features are stored on the way, so
+    that row 0 of the next rollout, where after_update carries them, needs no trunk."""
+    step = rollouts.step
+    observation, store = _step_observation(policy, rollouts)
+    prev_actions = {k: v[step] for k, v in rollouts.prev_actions.items()}
+    with torch.no_grad():
+        value = policy.get_value(observation, rollouts.recurrent_hidden_states[step], prev_actions,
+                                 rollouts.masks[step]).detach()
+    store()
+    return value
+
+
 def act_for_rollout(policy, rollouts, deterministic=False):
     """The action half of `_collect_rollout_step` (ddppo_waypoint_trainer.py:160-220) over any storage
     with the arenas (vlnce_amd.ActionDictRolloutStorage, or the reference's own class): slices the
@@ -91,17 +141,31 @@ def act_for_rollout(policy, rollouts, deterministic=False):
 
     When act() took its one-launch path (policy.fused_act / the "waypoint_act" option) the history is
     ONE launch that reads the choice on the device, and the predictions come from the host rows act()
-    already read back: no second synchronisation.  Otherwise this is the reference's loop."""
+    already read back: no second synchronisation.  Otherwise this is the reference's loop.
+
+    Over a storage with trunk-feature arenas (see _step_observation) the history gains
+    "rgb_history_features" / "depth_history_features": the chosen panorama slot's trunk output, or
+    trunk(zero frame) for STOP, from ONE launch that reads the choice on the device -- with either
+    act() path.  Put into the batch under those names beside `rgb_history` / `depth_history`
+    (ddppo_waypoint_trainer.py:237-238), `rollouts.insert(batch, ...)` stores them at step + 1 with
+    everything else."""
     from . import waypoint_act
 
     step = rollouts.step
-    observation = {k: v[step] for k, v in rollouts.observations.items()}
+    observation, store = _step_observation(policy, rollouts)
     prev_actions = {k: v[step] for k, v in rollouts.prev_actions.items()}
     with torch.no_grad():
         outputs = policy.act(observation, rollouts.recurrent_hidden_states[step], prev_actions,
                              rollouts.masks[step], deterministic=deterministic)
     _, actions, elements, _, variances, _, _, _ = outputs
+    store()
     frames = {k: observation[k] for k in ("rgb", "depth")}
+    feature_history = {}
+    if "trunk_feature_key" in observation:
+        feats = {s: rollouts.observations[s + "_features"][step] for s in SENSORS}
+        zeros = {s: policy.net.trunk_zero(s, frames[s].shape[-3:], frames[s].device,
+                                          observation["trunk_feature_key"]) for s in SENSORS}
+        feature_history = waypoint_act.feature_pick(feats, zeros, elements["pano"])
     predictions = {k: [] for k in ("distance_pred", "offset_pred", "distance_var", "offset_var")}
     rows = getattr(policy, "last_act_rows", None)
     if rows is not None:
@@ -112,6 +176,7 @@ def act_for_rollout(policy, rollouts, deterministic=False):
                 predictions["offset_pred"].append(row[waypoint_act.ROW_OFFSET])
                 predictions["distance_var"].append(row[waypoint_act.ROW_DISTANCE_VAR])
                 predictions["offset_var"].append(row[waypoint_act.ROW_OFFSET_VAR])
+        history.update(feature_history)
         return outputs, history, predictions
     history = {k: torch.zeros_like(v[:, 0]) for k, v in frames.items()}
     for i, action in enumerate(actions):
@@ -125,6 +190,7 @@ def act_for_rollout(policy, rollouts, deterministic=False):
             predictions[part + "_pred"].append(to_metric(elements[part][i]).item())
             var = variances[part]
             predictions[part + "_var"].append(var[i].item() if type(var) is torch.Tensor else var)
+    history.update(feature_history)
     return outputs, history, predictions
 
 
@@ -158,14 +224,42 @@ def wddppo_minibatch_update(policy, optimizer, sample, cfg=PPOConfig(), *, step_
     return tuple(stats[1:7].unbind(0))
 
 
+def _trunk_cache_usable(policy, rollouts):
+    """None when the update can run from the storage's trunk features, else why not (an exception)"""
+    if not getattr(rollouts, "has_trunk_features", False):
+        return RuntimeError("trunk-feature cache: the storage has no feature arenas "
+                            "(ActionDictRolloutStorage(trunk_features=...))")
+    missing = [r for r in range(rollouts.step) if not rollouts.trunk_valid[r]]
+    if missing or rollouts.trunk_key is None:
+        return RuntimeError(f"trunk-feature cache: rows {missing} of the storage hold no trunk features "
+                            "(collect with act_for_rollout / bootstrap_value)")
+    try:
+        now = policy.net.trunk_cache_key()
+        for s in SENSORS:
+            policy.net.check_trunk_cache(s, rollouts.trunk_key, now)
+    except RuntimeError as e:
+        return e
+    return None
+
+
 def wddppo_update(policy, optimizer, rollouts, cfg=PPOConfig(), *, ppo_epoch=2, num_mini_batch=4,
-                  use_normalized_advantage=False, grad_hook=None):
+                  use_normalized_advantage=False, grad_hook=None, use_trunk_cache=None):
     """WDDPPO.update (ddppo_alg.py:37-149) over any storage that has `recurrent_generator` and the
     arenas (vlnce_amd.ActionDictRolloutStorage, or the reference's own class): `ppo_epoch` passes of
     `num_mini_batch` minibatches, each through wddppo_minibatch_update.  The six statistics
     accumulate on the device and are read back ONCE, at the end (the reference calls .item() six
     times per minibatch); returns their means over the ppo_epoch * num_mini_batch updates:
-    (value_loss, action_loss, entropy_loss, pano / offset / distance entropy)."""
+    (value_loss, action_loss, entropy_loss, pano / offset / distance entropy).
+
+    use_trunk_cache: None = run the minibatches from the storage's trunk features (no frame is
+    gathered, no trunk runs) when it has them for every collected row under the net's current
+    trunk_cache_key(), else from the frames; True = raise instead of falling back; False = frames."""
+    cached = False
+    if use_trunk_cache or use_trunk_cache is None:
+        why_not = _trunk_cache_usable(policy, rollouts)
+        if why_not is not None and use_trunk_cache:
+            raise why_not
+        cached = why_not is None
     if hasattr(rollouts, "get_advantages"):
         advantages = rollouts.get_advantages(use_normalized_advantage)
     else:
@@ -173,7 +267,13 @@ def wddppo_update(policy, optimizer, rollouts, cfg=PPOConfig(), *, ppo_epoch=2, 
                                            use_normalized_advantage)
     totals = None
     for _e in range(ppo_epoch):
-        for sample in rollouts.recurrent_generator(advantages, num_mini_batch):
+        for sample in (rollouts.recurrent_generator(advantages, num_mini_batch, frames=False) if cached
+                       else rollouts.recurrent_generator(advantages, num_mini_batch)):
+            if cached:
+                sample[0]["trunk_feature_key"] = rollouts.trunk_key
+            elif getattr(rollouts, "has_trunk_features", False):   # the frame path takes no stored feature
+                for k in [k for k in sample[0] if k.endswith("_features") and k != "angle_features"]:
+                    del sample[0][k]
             stats = torch.stack(wddppo_minibatch_update(policy, optimizer, sample, cfg,
                                                         grad_hook=grad_hook))
             totals = stats if totals is None else totals + stats

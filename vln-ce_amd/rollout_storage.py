@@ -26,6 +26,7 @@ from . import _lib
 from ._lib import ROLLOUT_MAX_ENVS, ROLLOUT_MAX_FIELDS, RolloutCopyField, RolloutGatherField
 
 ACTION_KEYS = ("pano", "offset", "distance")
+FRAME_KEYS = ("rgb", "depth", "rgb_history", "depth_history")   # what the trunk-feature arenas stand in for
 EPS_PPO = 1e-5   # ddppo_alg.py:35
 
 
@@ -51,11 +52,19 @@ def _split(seq, n):
 class ActionDictRolloutStorage:
     """A RolloutStorage container for actions consisting of pano, offset, and distance components.
     `device=` allocates the arenas where they will live (at full size they are ~1.4 GB: filling them
-    on the host and moving them is a waste); `.to(device)` works as in the reference."""
+    on the host and moving them is a waste); `.to(device)` works as in the reference.
+
+    `trunk_features={"rgb": shape, "depth": shape}` (WaypointPredictionNet.trunk_feature_shapes()) adds
+    the arenas of the trunk-feature cache to `observations`: `<sensor>_features` [T+1, N, P, *shape] and
+    `<sensor>_history_features` [T+1, N, *shape], the outputs of the frozen visual trunks for the
+    frames beside them.  As observations they are carried by after_update and cut into minibatches
+    with everything else.  `trunk_valid[row]` says whether row's `<sensor>_features` were written
+    (ppo_harness.act_for_rollout / bootstrap_value do that), `trunk_key` under which
+    trunk_cache_key() of the net."""
 
     def __init__(self, num_steps, num_envs, observation_space, recurrent_hidden_state_size,
                  num_recurrent_layers=1, continuous_offset=True, continuous_distance=True, *,
-                 device=None):
+                 device=None, trunk_features=None):
         def zeros(*shape, dtype=torch.float32):
             return torch.zeros(*shape, dtype=dtype, device=device)
 
@@ -63,6 +72,15 @@ class ActionDictRolloutStorage:
         for sensor in observation_space.spaces:
             self.observations[sensor] = zeros(num_steps + 1, num_envs,
                                               *observation_space.spaces[sensor].shape)
+        self.has_trunk_features = trunk_features is not None
+        self.trunk_valid = [False] * (num_steps + 1)
+        self.trunk_key = None
+        if trunk_features is not None:
+            for sensor in ("rgb", "depth"):
+                P = observation_space.spaces[sensor].shape[0]
+                shape = tuple(trunk_features[sensor])
+                self.observations[sensor + "_features"] = zeros(num_steps + 1, num_envs, P, *shape)
+                self.observations[sensor + "_history_features"] = zeros(num_steps + 1, num_envs, *shape)
         self.recurrent_hidden_states = zeros(num_steps + 1, num_envs, num_recurrent_layers,
                                              recurrent_hidden_state_size)
         self.rewards = zeros(num_steps, num_envs, 1)
@@ -156,11 +174,13 @@ class ActionDictRolloutStorage:
         triples += [(self.action_log_probs, s, action_log_probs), (self.value_preds, s, value_preds),
                     (self.rewards, s, rewards), (self.masks, s + 1, masks)]
         self._copy_rows(triples)
+        self.trunk_valid[s + 1] = False   # (the row's frames are new; its features are not written yet)
         self.step = s + 1
 
     def after_update(self):
         if self.step != 0:   # (row 0 onto itself: nothing to move)
             self._copy_rows([(a, 0, self._row(a, self.step)) for a in self._carried])
+        self.trunk_valid = [self.trunk_valid[self.step]] + [False] * self.num_steps   # the flag moves with its row
         self.step = 0
 
     def compute_returns(self, next_value, use_gae, gamma, tau):
@@ -204,10 +224,16 @@ class ActionDictRolloutStorage:
                                 EPS_PPO)
         return adv
 
-    def recurrent_generator(self, advantages, num_mini_batch):
+    def trunk_rows_valid(self, key):
+        """whether every collected row [0, step) holds trunk features made under `key`"""
+        return (self.has_trunk_features and self.trunk_key is not None and self.trunk_key == key
+                and all(self.trunk_valid[:self.step]))
+
+    def recurrent_generator(self, advantages, num_mini_batch, frames=True):
         """The yielded `actions_batch` and `prev_actions_batch` are dictionaries with keys
         ["pano", "offset", "distance"] whose values are batched action elements.  Rows are
-        time-major, t * N' + j."""
+        time-major, t * N' + j.  frames=False leaves the raw-frame arenas (FRAME_KEYS) out of the
+        gather and out of the yielded observations: the trunk-feature arenas stand in for them."""
         num_processes = self.rewards.size(1)
         assert num_processes >= num_mini_batch, (
             "Trainer requires the number of processes ({}) "
@@ -218,7 +244,11 @@ class ActionDictRolloutStorage:
         perm = torch.randperm(num_processes)
         T, dev = self.step, self.returns.device
         adv = advantages.to(dev).contiguous()
+        sensors = [k for k in self.observations if frames or k not in FRAME_KEYS]
         arenas = self._batched + [(adv, False)]
+        if not frames:
+            assert self.has_trunk_features, "frames=False needs the trunk-feature arenas"
+            arenas = [(self.observations[k], False) for k in sensors] + arenas[len(self.observations):]
         lib = _L()
         for start_ind in range(0, num_processes, num_envs_per_batch):
             # (an indivisible count ends as the reference does: IndexError behind the full batches)
@@ -237,7 +267,7 @@ class ActionDictRolloutStorage:
                     lib.rollout_gather([RolloutGatherField(a, o, E, N, n, j0, once)
                                         for a, o, E, N, once in part], part_envs, max(T, 1))
             it = iter(outs)
-            observations_batch = {sensor: next(it) for sensor in self.observations}
+            observations_batch = {sensor: next(it) for sensor in sensors}
             recurrent_hidden_states_batch = next(it)
             actions_batch = {k: next(it) for k in self.actions}
             prev_actions_batch = {k: next(it) for k in self.actions}

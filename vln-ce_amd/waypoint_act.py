@@ -90,5 +90,19 @@ def history_pick(frames, pano):
     return outs
 
 
-__all__ = ["ActResult", "WP_ABSENT", "WP_CONTINUOUS", "WP_DISCRETE", "flag_errors", "history_pick",
-           "launch"]
+def feature_pick(features, zeros, pano):
+    """{sensor: [B, P, ...] fp32 trunk outputs (a slice of a rollout arena is fine)}, {sensor: [...]
+    trunk(zero frame)} and the panorama choice [B, 1] int64 ON THE DEVICE -> {sensor +
+    "_history_features": [B, ...]}: the chosen slot's features, `zeros[sensor]` for a STOP row.  One
+    launch for all sensors (vlnce_waypoint_feature_pick), no read-back."""
+    names = list(features)
+    B, P = features[names[0]].shape[:2]
+    outs = {k: torch.empty((B,) + tuple(v.shape[2:]), device=v.device, dtype=torch.float32)
+            for k, v in features.items()}
+    ops.L().waypoint_feature_pick([(features[k], zeros[k], outs[k]) for k in names],
+                                  pano.reshape(-1).contiguous(), B, P)
+    return {k + "_history_features": v for k, v in outs.items()}
+
+
+__all__ = ["ActResult", "WP_ABSENT", "WP_CONTINUOUS", "WP_DISCRETE", "feature_pick", "flag_errors",
+           "history_pick", "launch"]

@@ -180,6 +180,11 @@ class WaypointPredictionNet(Net):
         # kept out of the module tree (it shares our sub-modules): see _WaypointTail
         object.__setattr__(self, "_tail", GraphedTail(lambda: _WaypointTail(self)))
         self._branches = BranchStreams()
+        # one frame of each sensor as the observation space describes it, for the zero frame of the
+        # trunk-feature cache when a batch carries no frames at all
+        self._frame_shapes = {s: tuple(observation_space.spaces[s].shape[-3:]) for s in ("rgb", "depth")}
+        self._trunk_zero = {}            # sensor -> (key, trunk(zero frame))
+        self.last_trunk_features = {}    # sensor -> [B, P, h, w, C] of the last forward that ran a trunk
         self.train()
 
     # ---- class index -> metres / radians (waypoint_predictors.py:184-215)
@@ -245,17 +250,137 @@ class WaypointPredictionNet(Net):
         emb = emb.reshape(b, n, *emb.shape[1:])
         return emb[:, : self._num_panos], emb[:, self._num_panos]
 
+    # ---- cached trunk outputs (the DD-PPO loop's trunk-feature cache).  Both encoders are frozen and in
+    # eval mode while rollouts are collected and while the agent is updated
+    # (ddppo_waypoint_trainer.py:496,526-530), so a trunk's output is a fixed function of one frame:
+    # the observation keys `<sensor>_history_features` [B, h, w, C] (unmasked) and `<sensor>_features`
+    # [B, P, h, w, C] -- one frame's trunk output as its memory holds it, channels-last; the logical
+    # [.., C, h, w] view `trunk_features` returns is taken too -- stand in for the frames.
+    def trunk_feature_shapes(self):
+        """{sensor: (h, w, C)} of one frame's trunk output (the arenas of
+        ActionDictRolloutStorage(trunk_features=...))"""
+        c, h, w = self.depth_encoder.visual_encoder.output_shape
+        hr, wr = self.rgb_encoder.cnn.avgpool.out_hw
+        return {"rgb": (hr, wr, self.rgb_encoder.resnet_layer_size), "depth": (h, w, c)}
+
+    def _sensor_encoder(self, sensor):
+        return self.rgb_encoder if sensor == "rgb" else self.depth_encoder
+
+    def trunk_cache_key(self):
+        """what a stored trunk output depends on beside its frame, per sensor: the version of every
+        trunk parameter (read through the checked list: a rebound parameter is seen), the plane
+        format of the convolutions and whether every norm layer of the trunk is in eval mode"""
+        fmt = ops.plane_format()
+        return tuple((tuple(p._version for p in enc.trunk_parameters()), fmt,
+                      not any(m.training for m in enc.trunk_norms()))
+                     for enc in (self.rgb_encoder, self.depth_encoder))
+
+    def check_trunk_cache(self, sensor, made_under=None, now=None):
+        """raises unless the trunk of `sensor` is a fixed function of one frame, and -- given the
+        trunk_cache_key() under which stored features were made -- still the function that made them
+        (now: the current trunk_cache_key(), when the caller has it)"""
+        enc = self._sensor_encoder(sensor)
+        name = f"{sensor}_encoder"
+        if any(p.requires_grad for p in enc.trunk_parameters()):
+            raise RuntimeError(f"trunk-feature cache: a trunk parameter of {name} requires grad "
+                               "(the cache is for frozen encoders)")
+        if any(m.training for m in enc.trunk_norms() if isinstance(m, nn.modules.batchnorm._BatchNorm)):
+            raise RuntimeError(f"trunk-feature cache: a BatchNorm of {name} is in training mode "
+                               f"(batch statistics couple the frames; call {name}.eval())")
+        if made_under is not None:
+            k = ("rgb", "depth").index(sensor)
+            now = (self.trunk_cache_key() if now is None else now)[k]
+            if tuple(made_under)[k] != now:
+                what = [w for w, a, b in zip(("parameter versions", "plane format", "norm layers in eval mode"),
+                                             made_under[k], now) if a != b]
+                raise RuntimeError(f"trunk-feature cache: the stored features of {name} were made under "
+                                   f"another key ({', '.join(what)} changed since)")
+
+    def _trunk_rows(self, sensor, frames):
+        """the trunk of `sensor` over frames [N, H, W, C] or [N, F, H, W, C]: [N (, F), h, w, C]"""
+        y = self._sensor_encoder(sensor).trunk_features({sensor: frames})   # logical [n, C, h, w]
+        y = y.detach().permute(0, 2, 3, 1).contiguous()
+        return y.reshape(*frames.shape[:-3], *y.shape[1:])
+
+    def trunk_zero(self, sensor, frame_shape, device, now=None):
+        """trunk(one all-zero frame) [h, w, C]: what a done-masked or STOP history frame encodes to.
+        Computed once per trunk_cache_key() (`now`, when the caller has it) and frame shape."""
+        k = ("rgb", "depth").index(sensor)
+        key = ((self.trunk_cache_key() if now is None else now)[k], tuple(frame_shape), torch.device(device))
+        hit = self._trunk_zero.get(sensor)
+        if hit is None or hit[0] != key:
+            zero = self._trunk_rows(sensor, torch.zeros((1, *frame_shape), device=device))[0]
+            hit = self._trunk_zero[sensor] = (key, zero)
+        return hit[1]
+
+    def _features_hwc(self, sensor, t, lead):
+        """a feature tensor [*lead, h, w, C] (or its logical [*lead, C, h, w] view) as fp32 rows"""
+        h, w, c = self.trunk_feature_shapes()[sensor]
+        if tuple(t.shape[len(lead):]) != (h, w, c):
+            assert tuple(t.shape[len(lead):]) == (c, h, w), (sensor, tuple(t.shape))
+            t = t.movedim(-3, -1)
+        assert tuple(t.shape[:len(lead)]) == tuple(lead), (sensor, tuple(t.shape))
+        t = t.detach()
+        if t.dtype != torch.float32:
+            t = t.float()
+        return t if t[0].is_contiguous() else t.contiguous()
+
+    def _encode_cached(self, sensors, observations, masks):
+        """{sensor: (rows [B, 12, P, C], rows [B, P, C])} as _encode_frames gives them, from cached
+        trunk outputs: the history frame is not encoded, and with `<sensor>_features` no frame is.
+        ONE launch (vlnce_waypoint_feature_rows) assembles every sensor's [B * 13, ...] batch; the
+        encoder's own `<sensor>_features` branch takes over from there."""
+        P = self._num_panos
+        made_under = observations.get("trunk_feature_key")
+        now = self.trunk_cache_key()
+        B = masks.shape[0]
+        m = masks.reshape(-1)
+        if m.dtype not in (torch.uint8, torch.float32):
+            m = m.to(torch.uint8)
+        fields, outs = [], {}
+        for s in sensors:
+            self.check_trunk_cache(s, made_under, now)
+            hist = self._features_hwc(s, observations[s + "_history_features"], (B,))
+            if s + "_features" in observations:
+                pano = self._features_hwc(s, observations[s + "_features"], (B, P))
+            else:
+                pano = self.last_trunk_features[s] = self._trunk_rows(s, observations[s])
+            frame_shape = (tuple(observations[s].shape[-3:]) if s in observations
+                           else self._frame_shapes[s])
+            zero = self.trunk_zero(s, frame_shape, hist.device, now)
+            outs[s] = torch.empty((B, P + 1, *zero.shape), device=hist.device, dtype=torch.float32)
+            fields.append((pano, hist, zero, outs[s]))
+        ops.L().waypoint_feature_rows(fields, m.contiguous(), B, P)
+        res = {}
+        for s in sensors:
+            batch = outs[s].view(B * (P + 1), *outs[s].shape[2:]).permute(0, 3, 1, 2)
+            emb = rows_of(self._sensor_encoder(s)({s + "_features": batch}))
+            emb = emb.reshape(B, P + 1, *emb.shape[1:])
+            res[s] = (emb[:, :P], emb[:, P])
+        return res
+
     def forward(self, observations, rnn_states, prev_actions, masks, raw_pano_logits=False):
         """raw_pano_logits (internal, WaypointPolicy's one-launch evaluate_actions): the first result
-        is the tail's [B, P+1] logits themselves, not the Categorical over them."""
-        for k in ("rgb", "depth", "instruction", "rgb_history", "depth_history", "angle_features"):
-            assert k in observations
+        is the tail's [B, P+1] logits themselves, not the Categorical over them.
+
+        Optional observation keys `rgb_features`, `depth_features`, `rgb_history_features`,
+        `depth_history_features` (and `trunk_feature_key`, the trunk_cache_key() they were made
+        under): cached trunk outputs, see _encode_cached.  A forward that ran a trunk for the
+        panorama leaves its output on `last_trunk_features[sensor]`."""
         P = self._num_panos
-        assert observations["rgb"].shape[1] == P
-        assert observations["depth"].shape[1] == P
+        cached = [s for s in ("rgb", "depth") if s + "_history_features" in observations]
+        for s in ("rgb", "depth"):
+            if s + "_features" in observations:
+                assert s in cached, f"{s}_features without {s}_history_features"
+            else:
+                assert s in observations and observations[s].shape[1] == P
+                assert s in cached or s + "_history" in observations
+        for k in ("instruction", "angle_features"):
+            assert k in observations
         mc, wc = self.model_config, self.wypt_cfg
         hs = self._hidden_size
         half = hs // 2
+        self.last_trunk_features = {}
 
         # the instruction encoder (200-token RxR-length instructions: a 200-step recurrence on a
         # handful of workgroups, ~0.7 ms, and one host sync for the lengths) on a side stream under
@@ -263,10 +388,11 @@ class WaypointPredictionNet(Net):
         fork = self._branches.fork(rnn_states.device)
         ins, join_ins = self._branches.run(fork, 0, rnn_states.device,
                                            lambda: self.instruction_encoder(observations))
-        rgb, rgb_hist = self._encode_frames(self.rgb_encoder, "rgb", observations["rgb"],
-                                            observations["rgb_history"], masks)
-        dep, dep_hist = self._encode_frames(self.depth_encoder, "depth", observations["depth"],
-                                            observations["depth_history"], masks)
+        from_cache = self._encode_cached(cached, observations, masks) if cached else {}
+        rgb, rgb_hist = from_cache["rgb"] if "rgb" in from_cache else self._encode_frames(
+            self.rgb_encoder, "rgb", observations["rgb"], observations["rgb_history"], masks)
+        dep, dep_hist = from_cache["depth"] if "depth" in from_cache else self._encode_frames(
+            self.depth_encoder, "depth", observations["depth"], observations["depth_history"], masks)
         join_ins()
         ins = ins.permute(0, 2, 1)  # [B, L, C]
         B = rgb.shape[0]
