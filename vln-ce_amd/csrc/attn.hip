@@ -272,7 +272,11 @@ extern "C" int vlnce_attn_bwd(const float* dout, const float* q, const float* K,
                               float* dV, int lddv, int B, int P, int Dk, int Dv,
                               vlnce_stream_t stream) {
   VLNCE_CHECK_ARG(dout && q && K && V && attn, "attn_bwd: null argument");
-  VLNCE_CHECK_ARG(B > 0 && P > 0 && P <= MAXP, "attn_bwd: bad shape");
+  VLNCE_CHECK_ARG(B > 0 && P > 0 && P <= MAXP && Dk > 0 && Dv > 0, "attn_bwd: bad shape (P<=%d)",
+                  MAXP);
+  VLNCE_CHECK_ARG(mask_mode >= 0 && mask_mode <= 2, "attn_bwd: bad mask_mode");
+  VLNCE_CHECK_ARG((dK == nullptr || lddk >= Dk) && (dV == nullptr || lddv >= Dv),
+                  "attn_bwd: gradient row pitch below the row width");
   hipLaunchKernelGGL(attn_bwd_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      dout, q, K, ldk, V, ldv, mask, mask_mode, scale, attn, dq, dK, lddk, dV, lddv,
                      P, Dk, Dv, (const long long*)nullptr);
@@ -286,7 +290,11 @@ extern "C" int vlnce_attn_bwd_shared(const float* dout, const float* q, const fl
                                      float* dq, float* dK, int lddk, float* dV, int lddv, int B,
                                      int P, int Dk, int Dv, vlnce_stream_t stream) {
   VLNCE_CHECK_ARG(dout && q && K && V && attn && kv_index, "attn_bwd_shared: null argument");
-  VLNCE_CHECK_ARG(B > 0 && P > 0 && P <= MAXP, "attn_bwd_shared: bad shape");
+  VLNCE_CHECK_ARG(B > 0 && P > 0 && P <= MAXP && Dk > 0 && Dv > 0,
+                  "attn_bwd_shared: bad shape (P<=%d)", MAXP);
+  VLNCE_CHECK_ARG(mask_mode >= 0 && mask_mode <= 2, "attn_bwd_shared: bad mask_mode");
+  VLNCE_CHECK_ARG((dK == nullptr || lddk >= Dk) && (dV == nullptr || lddv >= Dv),
+                  "attn_bwd_shared: gradient row pitch below the row width");
   hipLaunchKernelGGL(attn_bwd_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      dout, q, K, ldk, V, ldv, mask, mask_mode, scale, attn, dq, dK, lddk, dV, lddv,
                      P, Dk, Dv, reinterpret_cast<const long long*>(kv_index));

@@ -758,6 +758,20 @@ def action_head(x, weight, bias=None, count_nans=True):
 
 
 # ----------------------------------------------------------------- attention
+def _attn_mask(mask, rows, P):
+    """The kernels read the mask as [rows, P] contiguous bytes.  bool and uint8 are that (a bool
+    is one byte, 0 or 1); a view is made contiguous; any other dtype or shape would be read as raw
+    bytes, so it is an error here, before any launch."""
+    if mask is None:
+        return None
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"attention mask must be bool or uint8, got {mask.dtype}")
+    if tuple(mask.shape) != (rows, P):
+        raise ValueError(f"attention mask must be [{rows}, {P}], got {list(mask.shape)}")
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
 class AttnFn(Function):
     """out[B,Dv] = softmax(mask(q K^T) * scale) V ; K [B,P,Dk], V [B,P,Dv] (views allowed).
     With `index` (int64 [B]): K [U,P,Dk], V [U,P,Dv], mask [U,P] are shared by groups of queries,
@@ -783,6 +797,7 @@ class AttnFn(Function):
         else:
             index = index.contiguous()
             assert index.dtype == torch.int64 and index.numel() == B
+        mask = _attn_mask(mask, U, P)
         out = torch.empty((B, Dv), device=q.device, dtype=torch.float32)
         attn = torch.empty((B, P), device=q.device, dtype=torch.float32)
         mm = 0 if mask is None else int(mask_mode)
@@ -834,6 +849,7 @@ class AttnKVFn(Function):
         B, P, D = kv.shape
         dv = D - dk
         ld = kv.stride(1)
+        mask = _attn_mask(mask, B, P)
         out = torch.empty((B, dv), device=q.device, dtype=torch.float32)
         attn = torch.empty((B, P), device=q.device, dtype=torch.float32)
         mm = 0 if mask is None else int(mask_mode)
